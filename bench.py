@@ -9,15 +9,24 @@ bytes resident in HBM (decode, Miller loop + final exponentiation, encode), then
 part — the RCCL all-gather of the result arrays named by the north star.  Batches shard by contiguous ranges, one
 process per GPU, no collective on the data path other than that gather (scaling: weak, 2^20 per GPU).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload emult|multpoly] [--batch-log2 B]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                       [--workload emult|multpoly] [--batch-log2 B]
+  A plain run sets up, runs W untimed and K timed steps and prints the result line — nothing else.
+  --full adds everything else the line can carry: the live PMC passes below, the mid-size batches, the secondary
+  operations (Encrypt, Add / Neg, MultConst, MultPoly, Decrypt on both levels, the 512-bit configs[0]), the CPU
+  baselines with their byte-for-byte comparisons and, with more than one rank, the strong-scaling block and the
+  sharded Decrypt.  --no-extra / --no-cpu-baseline / --no-live-traffic leave parts of --full out.
+  --dump-outputs DIR: after the timed steps, what the last timed step computed — the wire bytes of the result array a
+  caller receives — goes to DIR/<name>.npy (float32, one row per element; a fixed seeded sample of the rows, their
+  indices in DIR/<name>_rows.npy as float64).  Inputs are seeded: two runs with the same arguments compute the same.
   --gpus N with WORLD_SIZE unset: this process spawns N fresh rank processes of itself (before anything touches
   the GPU) with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, one per GPU, RCCL over xGMI between them.
   Under an external launcher (python -m torch.distributed.run ... bench.py --gpus N) the ranks come from the
   environment and --gpus must agree with WORLD_SIZE.
   --workload multpoly: BASELINE configs[4] — 2^14 MultPoly instances of 16x16 coefficient polynomials (2^22
   coefficient pairs) per job plus one AddPoly, sharded by polynomial across the GPUs (strong scaling).
-  On one GPU at the BASELINE size the run first measures the HBM-side traffic its line quotes: two child passes of
-  its own timed step under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE`, started before this process touches
+  With --full on one GPU at the BASELINE size the run first measures the HBM-side traffic its line quotes: two child
+  passes of its own timed step under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE`, started before this process touches
   the GPU (live_traffic; about 13 s; --no-live-traffic quotes the committed summary under profiles/ instead).
 """
 import argparse
@@ -174,7 +183,7 @@ def live_traffic(timeout_s=150.0, extras=False):
     """roofline.traffic of the headline kernel measured by THIS run (verdict r05, weak 6): before this process touches
     the GPU, two child passes of this command's own timed step — `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE`,
     separate passes, no tracing domain, the program itself after `--` (MI355X_MICROARCH.md, HBM section) — over
-    `bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra` (with `extras`: `--pmc-extras`, which adds ONE launch
+    a plain `bench.py --steps 1 --warmup 0` (with `extras`: `--pmc-extras`, which adds ONE launch
     each of the secondary kernels whose traffic the line quotes — the two Adds of 2^20, Decrypt's lifts at 2^16 and
     2^20: pmc_extras).  FETCH_SIZE is calibrated in the same pass on
     k_encode's known read volume (2 NL x 4 bytes per element of limb-major SoA at 2^20 elements), as
@@ -206,8 +215,7 @@ def live_traffic(timeout_s=150.0, extras=False):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, ctr.lower())
             cmd = [exe, "--pmc", ctr, "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable,
-                   os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--no-cpu-baseline",
-                   "--no-extra", "--no-live-traffic"] + (["--pmc-extras"] if extras else [])
+                   os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0"] + (["--pmc-extras"] if extras else [])
             proc = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL,
                                     start_new_session=True)
             try:
@@ -757,6 +765,28 @@ def emit_line(line):
         os.write(_JSON_FD, data)
 
 
+DUMP_ROWS = 16384          # rows of an output array kept by --dump-outputs (float32: 17 MB at 258 bytes per row)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` maps a name to (uint8 device tensor of wire bytes, bytes per row).  Each goes to
+    path/<name>.npy as float32, one row per element, one value per byte; of an array with more than DUMP_ROWS rows a
+    fixed sample of rows (seeded, sorted, the same for every run and build), whose indices go to path/<name>_rows.npy
+    as float64 (exact below 2^53)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, (t, row_bytes) in arrays.items():
+        rows = t.numel() // row_bytes
+        if rows > DUMP_ROWS:
+            idx = np.sort(np.random.default_rng(20240229).choice(rows, DUMP_ROWS, replace=False))
+        else:
+            idx = np.arange(rows)
+        sel = t.view(rows, row_bytes)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), sel.cpu().numpy().astype(np.float32))
+        np.save(os.path.join(path, name + "_rows.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -766,15 +796,24 @@ def main():
     ap.add_argument("--batch-log2", type=int, default=20, help="emult: pairs per GPU (log2)")
     ap.add_argument("--polys-log2", type=int, default=14, help="multpoly: polynomials in the whole job (log2)")
     ap.add_argument("--key", default="k1024")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary Encrypt / Decrypt measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the live PMC passes, the secondary operations, the CPU baselines and "
+                         "comparisons, and with several ranks the strong-scaling block and the sharded Decrypt")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; a seeded sample of the rows)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU legs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary Encrypt / Decrypt measurements")
     ap.add_argument("--decrypt-log2", type=int, nargs="+", default=[16, 20],
                     help="batch sizes (log2, at most 20) of the Decrypt measurement")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and gather even with one rank")
     ap.add_argument("--pmc-extras", action="store_true", help=argparse.SUPPRESS)   # the child passes of live_traffic only
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="quote roofline.traffic from the committed PMC summary instead of measuring it in two child passes")
+                    help="with --full: quote roofline.traffic from the committed PMC summary instead of measuring it in two child passes")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                                   # a plain run: the headline and nothing else
+        args.no_cpu_baseline = args.no_extra = args.no_live_traffic = True
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1 or os.environ.get("BGN_BENCH_SPAWN") == "1":     # the latter: rehearse the spawn with one rank
@@ -882,11 +921,14 @@ def main():
     kernel_name = eng.last_kernel_name()
     if use_dist:
         assert bool((gathered[0][lo * EB:hi * EB] == out).all().item()), "gather mismatch"
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after the last step: the gathered result array, or this GPU's own
+        dump_outputs(args.dump_outputs, {"emult_out": (gathered[0] if use_dist else out, EB)})
     gathered[0] = None
 
-    # ---- strong scaling: the SAME global batch of 2^20 pairs over the ranks (2^17 per GPU at 8 GPUs) ----
+    # ---- strong scaling (--full): the SAME global batch of 2^20 pairs over the ranks (2^17 per GPU at 8 GPUs) ----
     strong = None
-    if use_dist:
+    if use_dist and args.full:
         s_total = per_gpu
         s_lo, s_hi = shard_range(s_total, world, rank)
         s_cnt = s_hi - s_lo
@@ -910,20 +952,24 @@ def main():
     # sample of this rank's batch for the CPU leg (not timed): 4096 distinct pairs STRIDED over the batch (every
     # 256th pair at 2^20).  A lane of k_pairing owns a run of up to sixteen pairings that share one inversion, pair e
     # sitting at position e / 65536 of its lane's run: a prefix would check position 0 only.
-    nchk = min(count, 4096)
-    chk_stride = max(1, count // nchk)
-    sel = torch.arange(nchk, device=dev) * chk_stride
-    a_h = a.view(count, EB)[sel].cpu().numpy().tobytes()
-    b_h = b.view(count, EB)[sel].cpu().numpy().tobytes()
-    o_h = out.view(count, EB)[sel].cpu().numpy().tobytes()
-    distinct = len({a_h[i * EB:(i + 1) * EB] + b_h[i * EB:(i + 1) * EB] for i in range(nchk)})
-    run_positions = sorted({int(e) // 65536 for e in sel.tolist()}) if count > 65536 else [0]
+    checked = {}
+    if args.full:
+        nchk = min(count, 4096)
+        chk_stride = max(1, count // nchk)
+        sel = torch.arange(nchk, device=dev) * chk_stride
+        a_h = a.view(count, EB)[sel].cpu().numpy().tobytes()
+        b_h = b.view(count, EB)[sel].cpu().numpy().tobytes()
+        o_h = out.view(count, EB)[sel].cpu().numpy().tobytes()
+        distinct = len({a_h[i * EB:(i + 1) * EB] + b_h[i * EB:(i + 1) * EB] for i in range(nchk)})
+        run_positions = sorted({int(e) // 65536 for e in sel.tolist()}) if count > 65536 else [0]
+        checked = {"distinct_pairs_in_checked_sample": distinct, "checked_sample_stride": chk_stride,
+                   "checked_run_positions": run_positions}
 
     extra = dec = None
-    full = args.key == "k1024" and args.batch_log2 == 20
-    if args.pmc_extras and world == 1 and not use_dist and full:
+    at_baseline_size = args.key == "k1024" and args.batch_log2 == 20
+    if args.pmc_extras and world == 1 and not use_dist and at_baseline_size:
         pmc_extras(pk, fx, dev, cts, xs, out)
-    if not args.no_extra and world == 1 and not use_dist and full:
+    if not args.no_extra and world == 1 and not use_dist and at_baseline_size:
         extra, dec = secondary_metrics(pk, fx, dev, cts, xs, rs, [min(k, 20) for k in args.decrypt_log2],
                                        no_cpu=args.no_cpu_baseline, polys_log2=args.polys_log2, prods=out, live=live)
         extra["config0_512bit_128"] = config0_metrics(args.no_cpu_baseline)
@@ -943,10 +989,10 @@ def main():
         mads = syn.algorithmic_mads_per_pairing(
             fx, run=max(1, min(16, -(-count // 65536))),
             window={0: 2, 3: 3, 4: 4}.get(eng.get_option("miller_window"), 5))
-        traffic, traffic_src = committed_traffic() if full else (None, None)
+        traffic, traffic_src = committed_traffic() if at_baseline_size else (None, None)
         if traffic is not None:
             traffic_src += " (FETCH_SIZE + WRITE_SIZE per launch of 2^20 pairings)"
-        if live is not None and full:
+        if live is not None and at_baseline_size:
             traffic, traffic_src = live["hbm_bytes_per_launch"], live["source"]
         mad_rate = mads * count / (k_ms * 1e-3)
         if use_dist:
@@ -960,15 +1006,13 @@ def main():
                                    "Miller+final-exp) per MI355X; operands = Config 2's Encrypt outputs (random 40-bit "
                                    "m, full-length r) x a fixed permutation of them" % args.batch_log2,
                        "key": fx["name"], "fp_bits": int(fx["p"], 16).bit_length(), "limbs29": syn.limbs_for(int(fx["p"], 16)),
-                       "batch_per_gpu": per_gpu, "global_batch": total, "rccl_ranks": rccl_ranks,
-                       "distinct_pairs_in_checked_sample": distinct, "checked_sample_stride": chk_stride,
-                       "checked_run_positions": run_positions,
+                       "batch_per_gpu": per_gpu, "global_batch": total, "rccl_ranks": rccl_ranks, **checked,
                        "parallelism": ("batch-sharded x%d, one process per GPU + RCCL all-gather of results" % world)
                        if world > 1 else "single GPU"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "traffic_passes": ({k: live[k] for k in ("FETCH_SIZE_KB", "WRITE_SIZE_KB", "launches", "fetch_calibration", "seconds")}
-                                            if live is not None and full else None),
+                                            if live is not None and at_baseline_size else None),
                          "kernel": kernel_name, "kernel_ms": k_ms,
                          "algorithmic_bytes_per_pairing": alg_bytes, "note": "per GPU (rank 0's kernel)"},
             "roofline_valu": {"bound": "v_mad_u64_u32 issue", "mads_per_pairing": mads, "achieved": mad_rate,
@@ -1145,6 +1189,9 @@ def bench_multpoly(args, pk, fx, dev, world, rank, use_dist, rccl_ranks):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         assert bool((gathered[lo * (d1 + d2) * EB: hi * (d1 + d2) * EB] == prod).all().item()), "gather mismatch"
+    if args.dump_outputs and rank == 0:
+        # the product polynomials (all of them, gathered, with several ranks) and this rank's AddPoly sums
+        dump_outputs(args.dump_outputs, {"multpoly_prod": (gathered if use_dist else prod, EB), "multpoly_sum": (job.summ, EB)})
     if rank == 0:
         job.npoly = npoly // world if world > 1 else npoly      # entry() prices the whole job over `world` GPUs
         e = job.entry(fx, dt / args.steps, world) if npoly % world == 0 else None

@@ -163,6 +163,33 @@ def test_eight_ranks_one_dying_mid_gather_and_one_overrunning_the_cap(monkeypatc
         os.kill(int(open(tmp_path / "pid6").read()), 0)
 
 
+def test_dump_outputs_writes_a_fixed_sample_of_rows_as_float32(tmp_path):
+    """--dump-outputs: every array as float32 rows of wire bytes; of a long array the same sorted sample of rows in
+    every run, their indices beside it; a short array whole; within the size the option promises."""
+    import numpy as np
+    import torch
+    bench = _load()
+    rows, eb = bench.DUMP_ROWS + 3000, 6
+    big = (torch.arange(rows * eb, dtype=torch.int64) * 7 % 256).to(torch.uint8)
+    small = torch.arange(5 * eb, dtype=torch.uint8)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": (big, eb), "small": (small, eb)})
+    got, idx = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "big_rows.npy")
+    assert got.dtype == np.float32 and got.shape == (bench.DUMP_ROWS, eb) and idx.dtype == np.float64
+    assert (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < rows
+    assert (got == big.view(rows, eb).numpy()[idx.astype(np.int64)]).all()
+    assert (np.load(tmp_path / "b" / "big_rows.npy") == idx).all() and (np.load(tmp_path / "b" / "big.npy") == got).all()
+    assert (np.load(tmp_path / "a" / "small.npy") == small.view(5, eb).numpy()).all()
+    assert (np.load(tmp_path / "a" / "small_rows.npy") == np.arange(5)).all()
+    # the headline's result array at any batch size: DUMP_ROWS rows of 258 bytes (1024-bit wire elements) as float32
+    assert bench.DUMP_ROWS * 258 * 4 * 2 < 64 << 20
+
+
+def test_full_and_dump_outputs_are_options_of_the_command():
+    r = subprocess.run([sys.executable, BENCH, "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def test_live_traffic_falls_back_quietly(monkeypatch, tmp_path):
     """bench.py measures roofline.traffic itself in two rocprofv3 --pmc child passes; where that cannot work — no GPU
     here, so the child bench exits non-zero; no rocprofv3; a profiler already around this process; a pass that hangs

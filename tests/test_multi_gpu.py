@@ -276,7 +276,7 @@ def test_bench_one_rank_over_rccl():
     plaintexts and statuses — everything the driver's 2/4/8-GPU runs execute except a second GPU.  The rate has to
     be that of the undistributed call (the gather of one shard is a device copy)."""
     argv = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch-log2", "16", "--no-cpu-baseline"]
-    line = _bench_line(argv + ["--force-dist"], spawn=True)
+    line = _bench_line(argv + ["--full", "--force-dist"], spawn=True)
     _keep("r06_bench_dist1_line.json", line)
     assert line["n_gpus"] == 1 and line["config"]["rccl_ranks"] == 1 and line["scaling"] == "weak"
     assert line["config"]["global_batch"] == 1 << 16 and line["value"] > 0
@@ -290,7 +290,7 @@ def test_bench_one_rank_over_rccl():
     assert plain["roofline"]["kernel"] == line["roofline"]["kernel"]
     ok = all(abs(v / plain["value"] - 1) < 0.03 for v in (line["value"], strong["value"]))
     if not ok:                                        # two steps of 150 ms each: one noisy sample gets a second pair
-        line2 = _bench_line(argv + ["--force-dist"], spawn=True)
+        line2 = _bench_line(argv + ["--full", "--force-dist"], spawn=True)
         plain = _bench_line(argv + ["--no-extra"], spawn=False)
         line, strong = line2, line2["strong_2^16"]
     for v in (line["value"], strong["value"]):

@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/r05_pmc_encrypt}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --kernel-trace --output-format csv \
-  -d "$OUT/p1" -o p -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/p1.json" 2> "$OUT/p1.err" || exit 1
+  -d "$OUT/p1" -o p -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > "$OUT/p1.json" 2> "$OUT/p1.err" || exit 1
 f="$OUT/p1/p_counter_collection.csv"
 head -1 "$f" > "$f.tmp"; grep -E "k_g1_fixed_chain<|k_g1_add<|k_gt_pow<|k_bsgs_search<|k_fixedpair_build_batch<" "$f" >> "$f.tmp"; mv "$f.tmp" "$f"
 find "$OUT" -name "*kernel_trace.csv" -size +2M -delete

@@ -17,7 +17,7 @@ fi
 for lib in "$@"; do
   name=$(basename "$lib" .so)
   echo "== $name"
-  BGN_AMD_LIB="$lib" timeout -k 10 600 python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline ${AB_BENCH_ARGS} > "$OUT/${name}_line.json" 2> "$OUT/${name}.err" || { tail -5 "$OUT/${name}.err"; exit 1; }
+  BGN_AMD_LIB="$lib" timeout -k 10 600 python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline ${AB_BENCH_ARGS} > "$OUT/${name}_line.json" 2> "$OUT/${name}.err" || { tail -5 "$OUT/${name}.err"; exit 1; }
   python3 - "$OUT/${name}_line.json" <<'PY'
 import json, sys
 l = json.loads([x for x in open(sys.argv[1]) if x.startswith("{")][-1])

@@ -192,7 +192,7 @@ def replace_block(path, begin, end, text):
 
 replace_block(os.path.join(ROOT, "DESIGN.md"), "%s-table-begin" % tag, "%s-table-end" % tag, table)
 
-cmd_bench = "`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra`; extras: `--steps 1 --warmup 0 --no-cpu-baseline`"
+cmd_bench = "`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra`; extras: `--full --steps 1 --warmup 0 --no-cpu-baseline`"
 cmd_pmc = "`rocprofv3 --pmc FETCH_SIZE --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extra` (and `WRITE_SIZE`), separate passes, no tracing"
 readme_rows = [
     (f"`{tag}_bench_line.json`, `{tag}_bench_line_profiled.json`, `{tag}_bench_kernel_stats.csv`, `{tag}_extra_kernel_stats.csv`",
