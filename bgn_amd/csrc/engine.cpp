@@ -12,6 +12,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <initializer_list>
 #include <mutex>
 #include <unordered_map>
 #include <thread>
@@ -53,20 +54,6 @@ size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // lane offsets inside a limb row are 32-bit byte offsets (gmem.hpp): at most 2^28 elements per call
 constexpr size_t kMaxBatch = (size_t)1 << 28;
-
-struct CombArr {
-  const void* p;
-  size_t w;
-};
-// A small host-buffer call joins the context's combiner (combiner.hpp); *taken = false: the caller stages by itself.
-int combine_call(bgn_ctx* c, int op, int level, size_t count, CombArr in0, CombArr in1, CombArr in2, CombArr out0,
-                 CombArr out1, bool* taken);
-#define COMBINE(op, level, count, i0, i1, i2, o0, o1)                                        \
-  {                                                                                          \
-    bool taken_ = false;                                                                     \
-    const int rc_ = combine_call(c, op, level, count, i0, i1, i2, o0, o1, &taken_);          \
-    if (taken_) return rc_;                                                                  \
-  }
 
 }  // namespace
 
@@ -1254,114 +1241,6 @@ int bgn_make_l2_batch_dev(bgn_ctx* c, size_t count, const uint8_t* a, uint8_t* o
   return pairing_common(c, count, a, count, nullptr, 0, 1, 0, 0, out, (hipStream_t)stream);
 }
 
-// Host-buffer wrappers: stage through device memory, synchronous.
-namespace {
-// Staging buffers of the host-buffer entry points.  A small call (the reference's own shape: one element per
-// call) would otherwise spend more time in hipMalloc / hipFree than in its kernels, so buffers of up to 4 MB
-// are kept in a small per-device pool and handed out again; larger ones are allocated and freed per call.
-struct StagePool {
-  struct Slot {
-    void* p;
-    size_t cap;
-    int device;
-  };
-  std::mutex mu;
-  std::vector<Slot> free_list;
-  static constexpr size_t kMaxKeep = (size_t)4 << 20;
-  static constexpr size_t kMaxSlots = 32;
-  void* take(int device, size_t bytes, size_t* cap) {
-    std::lock_guard<std::mutex> lk(mu);
-    for (size_t i = 0; i < free_list.size(); ++i)
-      if (free_list[i].device == device && free_list[i].cap >= bytes && free_list[i].cap <= 4 * bytes + 4096) {
-        void* p = free_list[i].p;
-        *cap = free_list[i].cap;
-        free_list.erase(free_list.begin() + (long)i);
-        return p;
-      }
-    return nullptr;
-  }
-  bool give(int device, void* p, size_t cap) {
-    if (cap > kMaxKeep) return false;
-    std::lock_guard<std::mutex> lk(mu);
-    if (free_list.size() >= kMaxSlots) return false;
-    free_list.push_back(Slot{p, cap, device});
-    return true;
-  }
-};
-StagePool g_stage_pool;
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int device = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), device(o.device) { o.p = nullptr; }
-  ~DevBuf() {
-    if (p && !g_stage_pool.give(device, p, cap)) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    if (!bytes) bytes = 1;
-    (void)hipGetDevice(&device);
-    p = g_stage_pool.take(device, bytes, &cap);
-    if (p) return BGN_OK;
-    cap = bytes <= StagePool::kMaxKeep ? round_up(bytes, 4096) : bytes;
-    hipError_t e = hipMalloc(&p, cap);
-    if (e != hipSuccess) {
-      p = nullptr;
-      return fail(BGN_E_HIP, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
-    }
-    return BGN_OK;
-  }
-};
-}  // namespace
-
-int bgn_mult_batch(bgn_ctx* c, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be, size_t r_len,
-                   uint8_t* out) {
-  if (!c || (count && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
-  if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
-  if (!count) return BGN_OK;
-  COMBINE(COMB_MULT, 2, count, (CombArr{a, (size_t)2 * c->L}), (CombArr{b, (size_t)2 * c->L}), (CombArr{r_be, r_len}),
-          (CombArr{out, (size_t)2 * c->L}), (CombArr{nullptr, 0}));
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t eb = (size_t)2 * c->L * count;
-  DevBuf da, db, dout;
-  int rc;
-  if ((rc = da.alloc(eb)) || (rc = db.alloc(eb)) || (rc = dout.alloc(eb))) return rc;
-  HIP_TRY(hipMemcpy(da.p, a, eb, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(db.p, b, eb, hipMemcpyHostToDevice));
-  DevBuf dr;
-  if (r_be) {
-    if ((rc = dr.alloc(count * r_len))) return rc;
-    HIP_TRY(hipMemcpy(dr.p, r_be, count * r_len, hipMemcpyHostToDevice));
-  }
-  rc = bgn_mult_batch_dev(c, count, (const uint8_t*)da.p, (const uint8_t*)db.p, (const uint8_t*)dr.p, r_len,
-                          (uint8_t*)dout.p, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, dout.p, eb, hipMemcpyDeviceToHost));
-  return BGN_OK;
-}
-
-int bgn_make_l2_batch(bgn_ctx* c, size_t count, const uint8_t* a, uint8_t* out) {
-  if (!c || (count && (!a || !out))) return fail(BGN_E_ARG, "null argument");
-  if (!count) return BGN_OK;
-  COMBINE(COMB_MAKE_L2, 1, count, (CombArr{a, (size_t)2 * c->L}), (CombArr{nullptr, 0}), (CombArr{nullptr, 0}),
-          (CombArr{out, (size_t)2 * c->L}), (CombArr{nullptr, 0}));
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t eb = (size_t)2 * c->L * count;
-  DevBuf da, dout;
-  int rc;
-  if ((rc = da.alloc(eb)) || (rc = dout.alloc(eb))) return rc;
-  HIP_TRY(hipMemcpy(da.p, a, eb, hipMemcpyHostToDevice));
-  rc = bgn_make_l2_batch_dev(c, count, (const uint8_t*)da.p, (uint8_t*)dout.p, nullptr);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, dout.p, eb, hipMemcpyDeviceToHost));
-  return BGN_OK;
-}
-
 // ---- Add / Sub / Neg / MultConst / Encrypt ------------------------------------------------
 
 namespace {
@@ -2181,29 +2060,175 @@ int bgn_encrypt_batch_dev(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t 
   return BGN_OK;
 }
 
-// ---- host-buffer wrappers -------------------------------------------------------------------
+// ==== host-buffer entry points ================================================================================
+// The calls without a suffix take host arrays: each describes its arrays once (HostArr) and host_call below stages
+// them through device memory around the _dev entry point — by way of the combiner of concurrent small calls, the
+// chunked pipeline of large link-bound ones, or one blocking copy per array.  Synchronous.
 namespace {
-struct Staged {   // copies host arrays to the device and results back
-  std::vector<DevBuf> bufs;
-  int up(const void* host, size_t bytes, void** dev) {
-    bufs.emplace_back();
-    int rc = bufs.back().alloc(bytes);
-    if (rc) return rc;
-    *dev = bufs.back().p;
-    if (host && bytes) {
-      hipError_t e = hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice);
-      if (e != hipSuccess) return fail(BGN_E_HIP, "hipMemcpy H2D: %s", hipGetErrorString(e));
+// Staging buffers of the host-buffer entry points.  A small call (the reference's own shape: one element per
+// call) would otherwise spend more time in hipMalloc / hipFree than in its kernels, so buffers of up to 4 MB
+// are kept in a small per-device pool and handed out again; larger ones are allocated and freed per call.
+struct StagePool {
+  struct Slot {
+    void* p;
+    size_t cap;
+    int device;
+  };
+  std::mutex mu;
+  std::vector<Slot> free_list;
+  static constexpr size_t kMaxKeep = (size_t)4 << 20;
+  static constexpr size_t kMaxSlots = 32;
+  void* take(int device, size_t bytes, size_t* cap) {
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t i = 0; i < free_list.size(); ++i)
+      if (free_list[i].device == device && free_list[i].cap >= bytes && free_list[i].cap <= 4 * bytes + 4096) {
+        void* p = free_list[i].p;
+        *cap = free_list[i].cap;
+        free_list.erase(free_list.begin() + (long)i);
+        return p;
+      }
+    return nullptr;
+  }
+  bool give(int device, void* p, size_t cap) {
+    if (cap > kMaxKeep) return false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (free_list.size() >= kMaxSlots) return false;
+    free_list.push_back(Slot{p, cap, device});
+    return true;
+  }
+};
+StagePool g_stage_pool;
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  int device = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap), device(o.device) { o.p = nullptr; }
+  ~DevBuf() {
+    if (p && !g_stage_pool.give(device, p, cap)) (void)hipFree(p);
+  }
+  int alloc(size_t bytes) {
+    if (!bytes) bytes = 1;
+    (void)hipGetDevice(&device);
+    p = g_stage_pool.take(device, bytes, &cap);
+    if (p) return BGN_OK;
+    cap = bytes <= StagePool::kMaxKeep ? round_up(bytes, 4096) : bytes;
+    hipError_t e = hipMalloc(&p, cap);
+    if (e != hipSuccess) {
+      p = nullptr;
+      return fail(BGN_E_HIP, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
     }
     return BGN_OK;
   }
-  int down(void* host, const void* dev, size_t bytes) {
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(BGN_E_HIP, "hipMemcpy D2H: %s", hipGetErrorString(e));
-    return BGN_OK;
-  }
 };
-}  // namespace
+
+// One array of a host-buffer call.  A call lists its inputs first (in the order of the _dev entry point's operands),
+// then its outputs.  An optional array the caller left out (src and dst null) keeps its slot, with a null device
+// pointer, so the indices of the others do not move.
+struct HostArr {
+  const void* src;   // host input (nullptr: an output, or absent)
+  void* dst;         // host output (nullptr: an input, or absent)
+  size_t width;      // bytes per row
+  size_t rows;
+  bool present() const { return src || dst; }
+  size_t bytes() const { return width * rows; }
+};
+// The device side of a call: n rows (a chunk, a combined batch or the whole call) of the inputs in[] to the outputs
+// out[], in the order of the call's HostArr list, launched on `stream`.
+using DevCall = std::function<int(size_t n, uint8_t* const* in, uint8_t* const* out, hipStream_t stream)>;
+
+// The _dev entry point of a combinable operation (CombineOp); w[]: bytes per row of the inputs, the scalar lengths
+// among them.  The combiner, the pipeline and the one-shot path all launch through here.
+int comb_launch(bgn_ctx* c, int op, int level, const size_t* w, size_t n, uint8_t* const* in, uint8_t* const* out,
+                hipStream_t s) {
+  switch (op) {
+    case COMB_ENCRYPT: return bgn_encrypt_batch_dev(c, n, in[0], w[0], in[1], w[1], out[0], s);
+    case COMB_ADD:
+    case COMB_SUB: return addsub_dev(c, n, level, in[0], in[1], in[2], w[2], out[0], s, op == COMB_SUB);
+    case COMB_NEG: return bgn_neg_batch_dev(c, n, level, in[0], out[0], s);
+    case COMB_MULT: return bgn_mult_batch_dev(c, n, in[0], in[1], in[2], w[2], out[0], s);
+    case COMB_MAKE_L2: return bgn_make_l2_batch_dev(c, n, in[0], out[0], s);
+    case COMB_MULTCONST: return bgn_multconst_batch_dev(c, n, level, in[0], in[1], w[1], in[2], w[2], out[0], s);
+    case COMB_DECRYPT: return bgn_decrypt_batch_dev(c, n, level, in[0], (int64_t*)out[0], out[1], s);
+  }
+  return fail(BGN_E_ARG, "combiner: unknown operation");
+}
+
+// ---- the combiner of concurrent small host-buffer calls (combiner.hpp) -------------------------------------------
+Combiner* get_combiner(bgn_ctx* c) {
+  std::lock_guard<std::mutex> lk(c->mem_mu);
+  if (!c->comb) {
+    Combiner* cb = new (std::nothrow) Combiner();
+    if (!cb) return nullptr;
+    cb->launch = [c](const CombineKey& k, size_t n, uint8_t* const* in, uint8_t* const* out, void* s) {
+      const size_t w[3] = {k.w_in[0], k.w_in[1], k.w_in[2]};
+      return comb_launch(c, k.op, k.level, w, n, in, out, (hipStream_t)s);
+    };
+    cb->error_text = [] { return bgn_last_error(); };
+    cb->restore_error = [](const char* t) { g_err = t ? t : ""; };
+    CombinerBackend& be = cb->be;
+    be.bind = [c] { return hipSetDevice(c->device) == hipSuccess ? 0 : -1; };
+    be.stream_create = [](void** s) { return hipStreamCreateWithFlags((hipStream_t*)s, hipStreamNonBlocking) == hipSuccess ? 0 : -1; };
+    be.stream_destroy = [](void* s) { (void)hipStreamDestroy((hipStream_t)s); };
+    be.stream_sync = [](void* s) { return hipStreamSynchronize((hipStream_t)s) == hipSuccess ? 0 : -1; };
+    be.host_alloc = [](void** p, size_t b) {
+      if (hipHostMalloc(p, b, hipHostMallocDefault) == hipSuccess) return 0;
+      (void)hipGetLastError();
+      return -1;
+    };
+    be.host_free = [](void* p) { (void)hipHostFree(p); };
+    be.dev_alloc = [c](void** p, size_t b) {
+      if (ctx_malloc(c, p, b) == hipSuccess) return 0;
+      (void)hipGetLastError();
+      return -1;
+    };
+    be.dev_free = [c](void* p) { (void)ctx_wipe_free(c, p); };
+    be.dev_zero = [](void* p, size_t b) { return hipMemset(p, 0, b) == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -1; };
+    be.upload = [](void* d, const void* h, size_t b, void* s) {
+      return hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, (hipStream_t)s) == hipSuccess ? 0 : -1;
+    };
+    be.download = [](void* h, const void* d, size_t b, void* s) {
+      return hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, (hipStream_t)s) == hipSuccess ? 0 : -1;
+    };
+    c->comb = cb;
+  }
+  return c->comb;
+}
+
+// A small host-buffer call joins the context's combiner; *taken = false: the caller stages by itself.  A combinable
+// operation has one row per element in every array, at most three inputs and two outputs (CombineKey).
+int combine_call(bgn_ctx* c, int op, int level, const HostArr* arr, size_t n_in, size_t na, bool* taken) {
+  *taken = false;
+  const size_t count = arr[0].rows;
+  if (opt(c, &Options::combine) == 0 || (int64_t)count > opt(c, &Options::combine_max_count)) return BGN_OK;
+  CombineReq req;
+  req.key.op = op;
+  req.key.level = level;
+  req.count = count;
+  for (size_t i = 0; i < na; ++i) {
+    if (!arr[i].present()) continue;               // key width 0: absent
+    if (arr[i].width > 0xffffffffu) return BGN_OK;
+    if (i < n_in) {
+      req.key.w_in[i] = (uint32_t)arr[i].width;
+      req.in[i] = (const uint8_t*)arr[i].src;
+    } else {
+      req.key.w_out[i - n_in] = (uint32_t)arr[i].width;
+      req.out[i - n_in] = (uint8_t*)arr[i].dst;
+    }
+  }
+  Combiner* cb = get_combiner(c);
+  if (!cb) return BGN_OK;
+  *taken = true;
+  int64_t cap = opt(c, &Options::combine_max_batch);
+  if (cap < (int64_t)count) cap = (int64_t)count;
+  std::string err;
+  const int rc = cb->submit(req, (size_t)cap, opt(c, &Options::combine_wait_us), opt(c, &Options::combine_regroup_pct), &err);
+  if (rc) return fail(rc, "%s", err.c_str());
+  return BGN_OK;
+}
 
 // ---- chunked pipeline for the cheap element-wise operations on LARGE host arrays -------------------------------
 // Add / Sub / Neg on 2^18+ elements are bound by the PCIe link, not by their kernels (three 135 MB arrays against
@@ -2213,31 +2238,25 @@ struct Staged {   // copies host arrays to the device and results back
 // downloads chunk k-1, each on its own non-blocking stream, so both directions of the link stay busy and the
 // kernels hide under the copies.  Blocking hipMemcpy per helper keeps this correct for pageable arrays too (the
 // runtime stages those itself); page-locked arrays (bgn_host_alloc) move at the full link rate.
-namespace {
-struct PipeArray {
-  const uint8_t* src;   // host input (nullptr: this is an output)
-  uint8_t* dst;         // host output (nullptr: this is an input)
-  size_t stride;        // bytes per element
-};
+bool pipe_eligible(int op) { return op == COMB_ADD || op == COMB_SUB || op == COMB_NEG; }
+
 constexpr int kPipeSlots = 3;
 constexpr size_t kPipeChunkBytes = (size_t)48 << 20;   // of the widest array, rounded down to whole rounds of 65536 lanes
 
-size_t pipe_chunk(const bgn_ctx* c, const std::vector<PipeArray>& arrays, size_t count) {
+size_t pipe_chunk(const bgn_ctx* c, const HostArr* arrays, size_t na) {
   size_t widest = 1;
-  for (const PipeArray& a : arrays) widest = std::max(widest, a.stride);
+  for (size_t i = 0; i < na; ++i)
+    if (arrays[i].present()) widest = std::max(widest, arrays[i].width);
   size_t chunk = kPipeChunkBytes / widest;
   chunk = chunk >= 65536 ? (chunk / 65536) * 65536 : 65536;     // 131072 elements (34 MB) at a 1024-bit key
   if (opt(c, &Options::host_pipe_chunk) > 0) chunk = (size_t)opt(c, &Options::host_pipe_chunk);   // test hook: elements per chunk
-  (void)count;
   return chunk;
 }
 
-// op(n, dev, stream): dev[i] is the device chunk of arrays[i], n elements, launched on `stream`.
-// The caller holds c->pipe.mu.
-int host_pipeline(bgn_ctx* c, size_t count, const std::vector<PipeArray>& arrays, size_t chunk,
-                  const std::function<int(size_t, uint8_t* const*, hipStream_t)>& op) {
+// Every array has one row per element; the first n_in of them are the inputs.  The caller holds c->pipe.mu.
+int host_pipeline(bgn_ctx* c, const HostArr* arrays, size_t na, size_t n_in, size_t chunk, const DevCall& op) {
+  const size_t count = arrays[0].rows;
   const size_t nchunks = (count + chunk - 1) / chunk;
-  const size_t na = arrays.size();
   const bool trace = opt(c, &Options::host_pipe_trace) != 0;
   const auto t_begin = std::chrono::steady_clock::now();
   auto stamp = [&](const char* what, size_t k) {
@@ -2251,7 +2270,7 @@ int host_pipeline(bgn_ctx* c, size_t count, const std::vector<PipeArray>& arrays
     S.cap.resize(na * kPipeSlots, 0);
   }
   for (size_t i = 0; i < na * kPipeSlots; ++i) {
-    const size_t need = chunk * arrays[i % na].stride;
+    const size_t need = arrays[i % na].present() ? chunk * arrays[i % na].width : 0;
     if (S.cap[i] >= need) continue;
     if (S.buf[i]) (void)ctx_free(c, S.buf[i]);
     S.buf[i] = nullptr;
@@ -2275,11 +2294,8 @@ int host_pipeline(bgn_ctx* c, size_t count, const std::vector<PipeArray>& arrays
   }
   hipStream_t s_up = S.s_up, s_run = S.s_run, s_down = S.s_down;
   hipEvent_t* done = S.done;
-  struct Slot {
-    void* p;
-  };
-  std::vector<Slot> bufs(na * kPipeSlots);
-  for (size_t i = 0; i < bufs.size(); ++i) bufs[i].p = S.buf[i];
+  // the device chunk of array i in ring slot `slot` (null for an absent array)
+  auto ring = [&](size_t slot, size_t i) { return arrays[i].present() ? (uint8_t*)S.buf[slot * na + i] : nullptr; };
   stamp("set up", nchunks);
   std::mutex mu;
   std::condition_variable cv;
@@ -2307,8 +2323,8 @@ int host_pipeline(bgn_ctx* c, size_t count, const std::vector<PipeArray>& arrays
       const size_t n = span(k), slot = k % kPipeSlots;
       for (size_t i = 0; i < na; ++i) {
         if (!arrays[i].src) continue;
-        hipError_t e = hipMemcpyAsync(bufs[slot * na + i].p, arrays[i].src + k * chunk * arrays[i].stride,
-                                      n * arrays[i].stride, hipMemcpyHostToDevice, s_up);
+        hipError_t e = hipMemcpyAsync(ring(slot, i), (const uint8_t*)arrays[i].src + k * chunk * arrays[i].width,
+                                      n * arrays[i].width, hipMemcpyHostToDevice, s_up);
         if (e != hipSuccess) return set_err(BGN_E_HIP, hipGetErrorString(e));
       }
       hipError_t e = hipStreamSynchronize(s_up);
@@ -2333,7 +2349,7 @@ int host_pipeline(bgn_ctx* c, size_t count, const std::vector<PipeArray>& arrays
       hipError_t e = hipEventSynchronize(done[slot]);
       for (size_t i = 0; i < na && e == hipSuccess; ++i) {
         if (!arrays[i].dst) continue;
-        e = hipMemcpyAsync(arrays[i].dst + k * chunk * arrays[i].stride, bufs[slot * na + i].p, n * arrays[i].stride,
+        e = hipMemcpyAsync((uint8_t*)arrays[i].dst + k * chunk * arrays[i].width, ring(slot, i), n * arrays[i].width,
                            hipMemcpyDeviceToHost, s_down);
       }
       if (e == hipSuccess) e = hipStreamSynchronize(s_down);
@@ -2354,8 +2370,8 @@ int host_pipeline(bgn_ctx* c, size_t count, const std::vector<PipeArray>& arrays
       if (err.load() != BGN_OK) break;
     }
     const size_t slot = k % kPipeSlots;
-    for (size_t i = 0; i < na; ++i) dev[i] = (uint8_t*)bufs[slot * na + i].p;
-    int rc = op(span(k), dev.data(), s_run);
+    for (size_t i = 0; i < na; ++i) dev[i] = ring(slot, i);
+    int rc = op(span(k), dev.data(), dev.data() + n_in, s_run);
     if (rc == BGN_OK && hipEventRecord(done[slot], s_run) != hipSuccess) rc = fail(BGN_E_HIP, "hipEventRecord failed");
     if (rc != BGN_OK) {
       set_err(rc, bgn_last_error());
@@ -2385,74 +2401,96 @@ bool pipe_worthwhile(const bgn_ctx* c, size_t count, size_t chunk) {
   return count >= 2 * chunk;
 }
 
-int run_pipelined(bgn_ctx* c, size_t count, const std::vector<PipeArray>& arrays, size_t chunk,
-                  const std::function<int(size_t, uint8_t* const*, hipStream_t)>& op, bool* ran) {
+int run_pipelined(bgn_ctx* c, const HostArr* arrays, size_t na, size_t n_in, size_t chunk, const DevCall& op, bool* ran) {
   std::unique_lock<std::mutex> lk(c->pipe.mu, std::try_to_lock);
   *ran = lk.owns_lock();
   if (!*ran) return BGN_OK;            // another thread is in the pipeline of this context: stage in one shot
-  return host_pipeline(c, count, arrays, chunk, op);
+  return host_pipeline(c, arrays, na, n_in, chunk, op);
+}
+
+// The body of every host-buffer entry point, after its argument checks.  `op`: the CombineOp of a combinable
+// operation, which launches through comb_launch; 0: `call` is the device side (arrays without one row per element).
+int host_call(bgn_ctx* c, int op, int level, std::initializer_list<HostArr> list, const DevCall& call = nullptr) {
+  const HostArr* arr = list.begin();
+  const size_t na = list.size(), count = arr[0].rows;
+  size_t n_in = 0;
+  while (n_in < na && !arr[n_in].dst) ++n_in;
+  // a CombineKey, and w[] below, hold three inputs and two outputs; without an operation the caller brings the device side
+  if (op ? n_in > 3 || na - n_in > 2 : !call) return fail(BGN_E_ARG, "host_call: arrays do not fit the operation");
+  if (op) {
+    bool taken = false;
+    const int rc = combine_call(c, op, level, arr, n_in, na, &taken);
+    if (taken) return rc;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  size_t w[3] = {0, 0, 0};
+  for (size_t i = 0; op && i < n_in; ++i) w[i] = arr[i].width;
+  auto dev_call = [&](size_t n, uint8_t* const* in, uint8_t* const* out, hipStream_t s) {
+    return op ? comb_launch(c, op, level, w, n, in, out, s) : call(n, in, out, s);
+  };
+  if (pipe_eligible(op)) {
+    const size_t chunk = pipe_chunk(c, arr, na);
+    if (pipe_worthwhile(c, count, chunk)) {
+      bool ran = false;
+      const int rc = run_pipelined(c, arr, na, n_in, chunk, dev_call, &ran);
+      if (ran) return rc;
+    }
+  }
+  std::vector<DevBuf> bufs(na);
+  std::vector<uint8_t*> dev(na, nullptr);
+  for (size_t i = 0; i < na; ++i) {
+    if (!arr[i].present()) continue;
+    const int rc = bufs[i].alloc(arr[i].bytes());
+    if (rc) return rc;
+    dev[i] = (uint8_t*)bufs[i].p;
+    if (arr[i].src && arr[i].bytes()) HIP_TRY(hipMemcpy(dev[i], arr[i].src, arr[i].bytes(), hipMemcpyHostToDevice));
+  }
+  const int rc = dev_call(count, dev.data(), dev.data() + n_in, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  for (size_t i = 0; i < na; ++i)
+    if (arr[i].dst) HIP_TRY(hipMemcpy(arr[i].dst, dev[i], arr[i].bytes(), hipMemcpyDeviceToHost));
+  return BGN_OK;
+}
+
+int addsub_host(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
+                size_t r_len, uint8_t* out, bool subtract) {
+  if (!c || (count && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
+  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
+  if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, subtract ? COMB_SUB : COMB_ADD, level,
+                   {{a, nullptr, E, count}, {b, nullptr, E, count}, {r_be, nullptr, r_len, count}, {nullptr, out, E, count}});
 }
 }  // namespace
 
-#define UP(host, bytes, devp)                                  \
-  {                                                            \
-    int rc_ = S.up(host, bytes, (void**)&(devp));              \
-    if (rc_) return rc_;                                       \
-  }
+int bgn_mult_batch(bgn_ctx* c, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be, size_t r_len,
+                   uint8_t* out) {
+  if (!c || (count && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
+  if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, COMB_MULT, 2,
+                   {{a, nullptr, E, count}, {b, nullptr, E, count}, {r_be, nullptr, r_len, count}, {nullptr, out, E, count}});
+}
+
+int bgn_make_l2_batch(bgn_ctx* c, size_t count, const uint8_t* a, uint8_t* out) {
+  if (!c || (count && (!a || !out))) return fail(BGN_E_ARG, "null argument");
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, COMB_MAKE_L2, 1, {{a, nullptr, E, count}, {nullptr, out, E, count}});
+}
 
 int bgn_encrypt_batch(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* r_be, size_t r_len,
                       uint8_t* out) {
   if (!c || (count && (!x_be || !out))) return fail(BGN_E_ARG, "null argument");
   if (!x_len || (r_be && !r_len)) return fail(BGN_E_ARG, "zero scalar length");
   if (!count) return BGN_OK;
-  COMBINE(COMB_ENCRYPT, 1, count, (CombArr{x_be, x_len}), (CombArr{r_be, r_len}), (CombArr{nullptr, 0}),
-          (CombArr{out, (size_t)2 * c->L}), (CombArr{nullptr, 0}));
-  HIP_TRY(hipSetDevice(c->device));
-  Staged S;
-  S.bufs.reserve(4);
-  uint8_t *dx = nullptr, *dr = nullptr, *dout = nullptr;
-  UP(x_be, count * x_len, dx);
-  if (r_be) UP(r_be, count * r_len, dr);
-  UP(nullptr, count * 2 * (size_t)c->L, dout);
-  int rc = bgn_encrypt_batch_dev(c, count, dx, x_len, dr, r_len, dout, nullptr);
-  if (rc) return rc;
-  return S.down(out, dout, count * 2 * (size_t)c->L);
+  return host_call(c, COMB_ENCRYPT, 1,
+                   {{x_be, nullptr, x_len, count}, {r_be, nullptr, r_len, count}, {nullptr, out, 2 * (size_t)c->L, count}});
 }
 
-static int addsub_host(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
-                       size_t r_len, uint8_t* out, bool subtract) {
-  if (!c || (count && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
-  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
-  if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
-  if (!count) return BGN_OK;
-  COMBINE(subtract ? COMB_SUB : COMB_ADD, level, count, (CombArr{a, (size_t)2 * c->L}), (CombArr{b, (size_t)2 * c->L}),
-          (CombArr{r_be, r_len}), (CombArr{out, (size_t)2 * c->L}), (CombArr{nullptr, 0}));
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t eb = count * 2 * (size_t)c->L;
-  {
-    const size_t w = 2 * (size_t)c->L;
-    std::vector<PipeArray> arrays = {{a, nullptr, w}, {b, nullptr, w}, {nullptr, out, w}};
-    if (r_be) arrays.push_back({r_be, nullptr, r_len});
-    const size_t chunk = pipe_chunk(c, arrays, count);
-    if (pipe_worthwhile(c, count, chunk)) {
-      bool ran = false;
-      int rc = run_pipelined(c, count, arrays, chunk, [&](size_t n, uint8_t* const* d, hipStream_t s) {
-        return addsub_dev(c, n, level, d[0], d[1], r_be ? d[3] : nullptr, r_len, d[2], s, subtract);
-      }, &ran);
-      if (ran) return rc;
-    }
-  }
-  Staged S;
-  S.bufs.reserve(4);
-  uint8_t *da = nullptr, *db = nullptr, *dr = nullptr, *dout = nullptr;
-  UP(a, eb, da);
-  UP(b, eb, db);
-  if (r_be) UP(r_be, count * r_len, dr);
-  UP(nullptr, eb, dout);
-  int rc = addsub_dev(c, count, level, da, db, dr, r_len, dout, nullptr, subtract);
-  if (rc) return rc;
-  return S.down(out, dout, eb);
-}
 int bgn_add_batch(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
                   size_t r_len, uint8_t* out) {
   return addsub_host(c, count, level, a, b, r_be, r_len, out, false);
@@ -2461,55 +2499,105 @@ int bgn_sub_batch(bgn_ctx* c, size_t count, int level, const uint8_t* a, const u
                   size_t r_len, uint8_t* out) {
   return addsub_host(c, count, level, a, b, r_be, r_len, out, true);
 }
+
 int bgn_neg_batch(bgn_ctx* c, size_t count, int level, const uint8_t* a, uint8_t* out) {
   if (!c || (count && (!a || !out))) return fail(BGN_E_ARG, "null argument");
   if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
   if (!count) return BGN_OK;
-  COMBINE(COMB_NEG, level, count, (CombArr{a, (size_t)2 * c->L}), (CombArr{nullptr, 0}), (CombArr{nullptr, 0}),
-          (CombArr{out, (size_t)2 * c->L}), (CombArr{nullptr, 0}));
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t eb = count * 2 * (size_t)c->L;
-  {
-    const size_t w = 2 * (size_t)c->L;
-    std::vector<PipeArray> arrays = {{a, nullptr, w}, {nullptr, out, w}};
-    const size_t chunk = pipe_chunk(c, arrays, count);
-    if (pipe_worthwhile(c, count, chunk)) {
-      bool ran = false;
-      int rc = run_pipelined(c, count, arrays, chunk, [&](size_t n, uint8_t* const* d, hipStream_t s) {
-        return bgn_neg_batch_dev(c, n, level, d[0], d[1], s);
-      }, &ran);
-      if (ran) return rc;
-    }
-  }
-  Staged S;
-  S.bufs.reserve(2);
-  uint8_t *da = nullptr, *dout = nullptr;
-  UP(a, eb, da);
-  UP(nullptr, eb, dout);
-  int rc = bgn_neg_batch_dev(c, count, level, da, dout, nullptr);
-  if (rc) return rc;
-  return S.down(out, dout, eb);
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, COMB_NEG, level, {{a, nullptr, E, count}, {nullptr, out, E, count}});
 }
+
 int bgn_multconst_batch(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint8_t* k_be, size_t k_len,
                         const uint8_t* r_be, size_t r_len, uint8_t* out) {
   if (!c || (count && (!a || !k_be || !out))) return fail(BGN_E_ARG, "null argument");
   if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
   if (!k_len || (r_be && !r_len)) return fail(BGN_E_ARG, "zero scalar length");
   if (!count) return BGN_OK;
-  COMBINE(COMB_MULTCONST, level, count, (CombArr{a, (size_t)2 * c->L}), (CombArr{k_be, k_len}), (CombArr{r_be, r_len}),
-          (CombArr{out, (size_t)2 * c->L}), (CombArr{nullptr, 0}));
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t eb = count * 2 * (size_t)c->L;
-  Staged S;
-  S.bufs.reserve(4);
-  uint8_t *da = nullptr, *dk = nullptr, *dr = nullptr, *dout = nullptr;
-  UP(a, eb, da);
-  UP(k_be, count * k_len, dk);
-  if (r_be) UP(r_be, count * r_len, dr);
-  UP(nullptr, eb, dout);
-  int rc = bgn_multconst_batch_dev(c, count, level, da, dk, k_len, dr, r_len, dout, nullptr);
-  if (rc) return rc;
-  return S.down(out, dout, eb);
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, COMB_MULTCONST, level,
+                   {{a, nullptr, E, count}, {k_be, nullptr, k_len, count}, {r_be, nullptr, r_len, count}, {nullptr, out, E, count}});
+}
+
+int bgn_decrypt_batch(bgn_ctx* c, size_t count, int level, const uint8_t* ct, int64_t* m, uint8_t* status) {
+  if (!c || (count && (!ct || !m || !status))) return fail(BGN_E_ARG, "null argument");
+  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
+  if (!c->have_secret) return fail(BGN_E_STATE, "secret key not set");
+  if (!c->have_tables) return fail(BGN_E_STATE, "DL tables not computed!");          // gsbs.go:56-58 (panic)
+  if (!count) return BGN_OK;
+  return host_call(c, COMB_DECRYPT, level,
+                   {{ct, nullptr, 2 * (size_t)c->L, count}, {nullptr, m, 8, count}, {nullptr, status, 1, count}});
+}
+
+// The remaining calls have no CombineOp (the rows of a poly_* array are whole polynomials, not elements): each passes
+// its _dev entry point as the device side.
+int bgn_poly_mult_batch(bgn_ctx* c, size_t npoly, size_t d1, size_t d2, const uint8_t* a, const uint8_t* b,
+                        uint8_t* out) {
+  if (!c || (npoly && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
+  if (!npoly) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0, {{a, nullptr, d1 * E, npoly}, {b, nullptr, d2 * E, npoly}, {nullptr, out, (d1 + d2) * E, npoly}},
+                   [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_poly_mult_batch_dev(c, npoly, d1, d2, in[0], in[1], o[0], s);
+                   });
+}
+
+int bgn_poly_multconst_batch(bgn_ctx* c, size_t npoly, size_t d, size_t dp, int level, const uint8_t* ct,
+                             const uint8_t* p_be, size_t k_len, int k_per_poly, uint8_t* out) {
+  if (!c || (npoly && (!ct || !p_be || !out))) return fail(BGN_E_ARG, "null argument");
+  if (!npoly) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0,
+                   {{ct, nullptr, d * E, npoly}, {p_be, nullptr, dp * k_len, k_per_poly ? npoly : 1},
+                    {nullptr, out, (d + dp) * E, npoly}},
+                   [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_poly_multconst_batch_dev(c, npoly, d, dp, level, in[0], in[1], k_len, k_per_poly, o[0], s);
+                   });
+}
+
+int bgn_poly_eval_batch(bgn_ctx* c, size_t npoly, size_t d, int level, const uint8_t* ct, uint64_t base, uint8_t* out) {
+  if (!c || (npoly && (!ct || !out))) return fail(BGN_E_ARG, "null argument");
+  if (!npoly) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0, {{ct, nullptr, d * E, npoly}, {nullptr, out, E, npoly}},
+                   [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_poly_eval_batch_dev(c, npoly, d, level, in[0], base, o[0], s);
+                   });
+}
+
+int bgn_validate_batch(bgn_ctx* c, size_t count, int level, const uint8_t* in, uint8_t* ok) {
+  if (!c || (count && (!in || !ok))) return fail(BGN_E_ARG, "null argument");
+  if (!count) return BGN_OK;
+  return host_call(c, 0, 0, {{in, nullptr, 2 * (size_t)c->L, count}, {nullptr, ok, 1, count}},
+                   [&](size_t n, uint8_t* const* i, uint8_t* const* o, hipStream_t s) {
+                     return bgn_validate_batch_dev(c, n, level, i[0], o[0], s);
+                   });
+}
+
+int bgn_check_decryption_proof_batch(bgn_ctx* c, size_t count, const uint8_t* ct, const uint8_t* v_be, size_t v_len,
+                                     const uint8_t* r_be, size_t r_len, uint8_t* ok) {
+  if (!c || (count && (!ct || !v_be || !r_be || !ok))) return fail(BGN_E_ARG, "null argument");
+  if (!count) return BGN_OK;
+  return host_call(c, 0, 0,
+                   {{ct, nullptr, 2 * (size_t)c->L, count}, {v_be, nullptr, v_len, count}, {r_be, nullptr, r_len, count},
+                    {nullptr, ok, 1, count}},
+                   [&](size_t n, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_check_decryption_proof_batch_dev(c, n, in[0], in[1], v_len, in[2], r_len, o[0], s);
+                   });
+}
+
+int bgn_check_plaintext_knowledge_batch(bgn_ctx* c, size_t count, const uint8_t* ct, const uint8_t* nonce,
+                                        const uint8_t* c_be, size_t c_len, const uint8_t* dl_be, size_t dl_len,
+                                        uint8_t* ok) {
+  if (!c || (count && (!ct || !nonce || !c_be || !dl_be || !ok))) return fail(BGN_E_ARG, "null argument");
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0,
+                   {{ct, nullptr, E, count}, {nonce, nullptr, E, count}, {c_be, nullptr, c_len, count},
+                    {dl_be, nullptr, dl_len, count}, {nullptr, ok, 1, count}},
+                   [&](size_t n, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_check_plaintext_knowledge_batch_dev(c, n, in[0], in[1], in[2], c_len, in[3], dl_len, o[0], s);
+                   });
 }
 
 // ---- Decrypt ---------------------------------------------------------------------------------
@@ -2661,28 +2749,6 @@ static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct,
   }
   HIP_TRY(hipGetLastError());
   return BGN_OK;
-}
-
-int bgn_decrypt_batch(bgn_ctx* c, size_t count, int level, const uint8_t* ct, int64_t* m, uint8_t* status) {
-  if (!c || (count && (!ct || !m || !status))) return fail(BGN_E_ARG, "null argument");
-  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
-  if (!c->have_secret) return fail(BGN_E_STATE, "secret key not set");
-  if (!c->have_tables) return fail(BGN_E_STATE, "DL tables not computed!");          // gsbs.go:56-58 (panic)
-  if (!count) return BGN_OK;
-  COMBINE(COMB_DECRYPT, level, count, (CombArr{ct, (size_t)2 * c->L}), (CombArr{nullptr, 0}), (CombArr{nullptr, 0}),
-          (CombArr{m, 8}), (CombArr{status, 1}));
-  HIP_TRY(hipSetDevice(c->device));
-  Staged S;
-  S.bufs.reserve(3);
-  uint8_t *dct = nullptr, *dst = nullptr;
-  int64_t* dm = nullptr;
-  UP(ct, count * 2 * (size_t)c->L, dct);
-  UP(nullptr, count * 8, dm);
-  UP(nullptr, count, dst);
-  int rc = bgn_decrypt_batch_dev(c, count, level, dct, dm, dst, nullptr);
-  if (rc) return rc;
-  if ((rc = S.down(m, dm, count * 8))) return rc;
-  return S.down(status, dst, count);
 }
 
 // ---- MultPoly --------------------------------------------------------------------------------
@@ -3027,23 +3093,6 @@ int bgn_poly_mult_batch_dev(bgn_ctx* c, size_t npoly, size_t d1, size_t d2, cons
   return BGN_OK;
 }
 
-int bgn_poly_mult_batch(bgn_ctx* c, size_t npoly, size_t d1, size_t d2, const uint8_t* a, const uint8_t* b,
-                        uint8_t* out) {
-  if (!c || (npoly && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
-  if (!npoly) return BGN_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t E = 2 * (size_t)c->L;
-  Staged S;
-  S.bufs.reserve(3);
-  uint8_t *da = nullptr, *db = nullptr, *dout = nullptr;
-  UP(a, npoly * d1 * E, da);
-  UP(b, npoly * d2 * E, db);
-  UP(nullptr, npoly * (d1 + d2) * E, dout);
-  int rc = bgn_poly_mult_batch_dev(c, npoly, d1, d2, da, db, dout, nullptr);
-  if (rc) return rc;
-  return S.down(out, dout, npoly * (d1 + d2) * E);
-}
-
 // ---- MultConstPoly / EvalPoly ---------------------------------------------------------------------
 namespace {
 int poly_lin_common(bgn_ctx* c, size_t npoly, size_t d, size_t dp, int level, const uint8_t* ct, const uint8_t* k_dev,
@@ -3122,38 +3171,6 @@ int bgn_poly_eval_batch_dev(bgn_ctx* c, size_t npoly, size_t d, int level, const
   return poly_lin_common(c, npoly, d, 0, level, ct, nullptr, &kb, k_len, 0, out, (hipStream_t)stream);
 }
 
-int bgn_poly_multconst_batch(bgn_ctx* c, size_t npoly, size_t d, size_t dp, int level, const uint8_t* ct,
-                             const uint8_t* p_be, size_t k_len, int k_per_poly, uint8_t* out) {
-  if (!c || (npoly && (!ct || !p_be || !out))) return fail(BGN_E_ARG, "null argument");
-  if (!npoly) return BGN_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t E = 2 * (size_t)c->L;
-  Staged S;
-  S.bufs.reserve(3);
-  uint8_t *dct = nullptr, *dk = nullptr, *dout = nullptr;
-  UP(ct, npoly * d * E, dct);
-  UP(p_be, (k_per_poly ? npoly : 1) * dp * k_len, dk);
-  UP(nullptr, npoly * (d + dp) * E, dout);
-  int rc = bgn_poly_multconst_batch_dev(c, npoly, d, dp, level, dct, dk, k_len, k_per_poly, dout, nullptr);
-  if (rc) return rc;
-  return S.down(out, dout, npoly * (d + dp) * E);
-}
-
-int bgn_poly_eval_batch(bgn_ctx* c, size_t npoly, size_t d, int level, const uint8_t* ct, uint64_t base, uint8_t* out) {
-  if (!c || (npoly && (!ct || !out))) return fail(BGN_E_ARG, "null argument");
-  if (!npoly) return BGN_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t E = 2 * (size_t)c->L;
-  Staged S;
-  S.bufs.reserve(2);
-  uint8_t *dct = nullptr, *dout = nullptr;
-  UP(ct, npoly * d * E, dct);
-  UP(nullptr, npoly * E, dout);
-  int rc = bgn_poly_eval_batch_dev(c, npoly, d, level, dct, base, dout, nullptr);
-  if (rc) return rc;
-  return S.down(out, dout, npoly * E);
-}
-
 // ---- input validation ---------------------------------------------------------------------------
 int bgn_validate_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* in, uint8_t* ok, void* stream) {
   if (!c || (count && (!in || !ok))) return fail(BGN_E_ARG, "null argument");
@@ -3164,20 +3181,6 @@ int bgn_validate_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* i
   c->kt->validate((hipStream_t)stream, c->d_params, in, c->L, count, level, ok);
   HIP_TRY(hipGetLastError());
   return BGN_OK;
-}
-
-int bgn_validate_batch(bgn_ctx* c, size_t count, int level, const uint8_t* in, uint8_t* ok) {
-  if (!c || (count && (!in || !ok))) return fail(BGN_E_ARG, "null argument");
-  if (!count) return BGN_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  Staged S;
-  S.bufs.reserve(2);
-  uint8_t *din = nullptr, *dok = nullptr;
-  UP(in, count * 2 * (size_t)c->L, din);
-  UP(nullptr, count, dok);
-  int rc = bgn_validate_batch_dev(c, count, level, din, dok, nullptr);
-  if (rc) return rc;
-  return S.down(ok, dok, count);
 }
 
 // ---- proof verification (gadgets.go) --------------------------------------------------------------
@@ -3239,130 +3242,6 @@ int bgn_check_plaintext_knowledge_batch_dev(bgn_ctx* c, size_t count, const uint
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return BGN_OK;
 }
-
-int bgn_check_decryption_proof_batch(bgn_ctx* c, size_t count, const uint8_t* ct, const uint8_t* v_be, size_t v_len,
-                                     const uint8_t* r_be, size_t r_len, uint8_t* ok) {
-  if (!c || (count && (!ct || !v_be || !r_be || !ok))) return fail(BGN_E_ARG, "null argument");
-  if (!count) return BGN_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  Staged S;
-  S.bufs.reserve(4);
-  uint8_t *dct = nullptr, *dv = nullptr, *dr = nullptr, *dok = nullptr;
-  UP(ct, count * 2 * (size_t)c->L, dct);
-  UP(v_be, count * v_len, dv);
-  UP(r_be, count * r_len, dr);
-  UP(nullptr, count, dok);
-  int rc = bgn_check_decryption_proof_batch_dev(c, count, dct, dv, v_len, dr, r_len, dok, nullptr);
-  if (rc) return rc;
-  return S.down(ok, dok, count);
-}
-
-int bgn_check_plaintext_knowledge_batch(bgn_ctx* c, size_t count, const uint8_t* ct, const uint8_t* nonce,
-                                        const uint8_t* c_be, size_t c_len, const uint8_t* dl_be, size_t dl_len,
-                                        uint8_t* ok) {
-  if (!c || (count && (!ct || !nonce || !c_be || !dl_be || !ok))) return fail(BGN_E_ARG, "null argument");
-  if (!count) return BGN_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t eb = count * 2 * (size_t)c->L;
-  Staged S;
-  S.bufs.reserve(5);
-  uint8_t *dct = nullptr, *dn = nullptr, *dc = nullptr, *dd = nullptr, *dok = nullptr;
-  UP(ct, eb, dct);
-  UP(nonce, eb, dn);
-  UP(c_be, count * c_len, dc);
-  UP(dl_be, count * dl_len, dd);
-  UP(nullptr, count, dok);
-  int rc = bgn_check_plaintext_knowledge_batch_dev(c, count, dct, dn, dc, c_len, dd, dl_len, dok, nullptr);
-  if (rc) return rc;
-  return S.down(ok, dok, count);
-}
-
-// ---- the combiner of concurrent small host-buffer calls (combiner.hpp) -------------------------------------------
-namespace {
-int comb_launch(bgn_ctx* c, const CombineKey& k, size_t n, uint8_t* const* in, uint8_t* const* out, hipStream_t s) {
-  switch (k.op) {
-    case COMB_ENCRYPT: return bgn_encrypt_batch_dev(c, n, in[0], k.w_in[0], in[1], k.w_in[1], out[0], s);
-    case COMB_ADD: return addsub_dev(c, n, k.level, in[0], in[1], in[2], k.w_in[2], out[0], s, false);
-    case COMB_SUB: return addsub_dev(c, n, k.level, in[0], in[1], in[2], k.w_in[2], out[0], s, true);
-    case COMB_NEG: return bgn_neg_batch_dev(c, n, k.level, in[0], out[0], s);
-    case COMB_MULT: return bgn_mult_batch_dev(c, n, in[0], in[1], in[2], k.w_in[2], out[0], s);
-    case COMB_MAKE_L2: return bgn_make_l2_batch_dev(c, n, in[0], out[0], s);
-    case COMB_MULTCONST: return bgn_multconst_batch_dev(c, n, k.level, in[0], in[1], k.w_in[1], in[2], k.w_in[2], out[0], s);
-    case COMB_DECRYPT: return bgn_decrypt_batch_dev(c, n, k.level, in[0], (int64_t*)out[0], out[1], s);
-  }
-  return fail(BGN_E_ARG, "combiner: unknown operation");
-}
-
-Combiner* get_combiner(bgn_ctx* c) {
-  std::lock_guard<std::mutex> lk(c->mem_mu);
-  if (!c->comb) {
-    Combiner* cb = new (std::nothrow) Combiner();
-    if (!cb) return nullptr;
-    cb->launch = [c](const CombineKey& k, size_t n, uint8_t* const* in, uint8_t* const* out, void* s) {
-      return comb_launch(c, k, n, in, out, (hipStream_t)s);
-    };
-    cb->error_text = [] { return bgn_last_error(); };
-    cb->restore_error = [](const char* t) { g_err = t ? t : ""; };
-    CombinerBackend& be = cb->be;
-    be.bind = [c] { return hipSetDevice(c->device) == hipSuccess ? 0 : -1; };
-    be.stream_create = [](void** s) { return hipStreamCreateWithFlags((hipStream_t*)s, hipStreamNonBlocking) == hipSuccess ? 0 : -1; };
-    be.stream_destroy = [](void* s) { (void)hipStreamDestroy((hipStream_t)s); };
-    be.stream_sync = [](void* s) { return hipStreamSynchronize((hipStream_t)s) == hipSuccess ? 0 : -1; };
-    be.host_alloc = [](void** p, size_t b) {
-      if (hipHostMalloc(p, b, hipHostMallocDefault) == hipSuccess) return 0;
-      (void)hipGetLastError();
-      return -1;
-    };
-    be.host_free = [](void* p) { (void)hipHostFree(p); };
-    be.dev_alloc = [c](void** p, size_t b) {
-      if (ctx_malloc(c, p, b) == hipSuccess) return 0;
-      (void)hipGetLastError();
-      return -1;
-    };
-    be.dev_free = [c](void* p) { (void)ctx_wipe_free(c, p); };
-    be.dev_zero = [](void* p, size_t b) { return hipMemset(p, 0, b) == hipSuccess && hipDeviceSynchronize() == hipSuccess ? 0 : -1; };
-    be.upload = [](void* d, const void* h, size_t b, void* s) {
-      return hipMemcpyAsync(d, h, b, hipMemcpyHostToDevice, (hipStream_t)s) == hipSuccess ? 0 : -1;
-    };
-    be.download = [](void* h, const void* d, size_t b, void* s) {
-      return hipMemcpyAsync(h, d, b, hipMemcpyDeviceToHost, (hipStream_t)s) == hipSuccess ? 0 : -1;
-    };
-    c->comb = cb;
-  }
-  return c->comb;
-}
-
-int combine_call(bgn_ctx* c, int op, int level, size_t count, CombArr in0, CombArr in1, CombArr in2, CombArr out0,
-                 CombArr out1, bool* taken) {
-  *taken = false;
-  if (opt(c, &Options::combine) == 0 || (int64_t)count > opt(c, &Options::combine_max_count)) return BGN_OK;
-  const CombArr ins[3] = {in0, in1, in2}, outs[2] = {out0, out1};
-  CombineReq req;
-  req.key.op = op;
-  req.key.level = level;
-  req.count = count;
-  for (int k = 0; k < 3; ++k)
-    if (ins[k].p) {
-      if (ins[k].w > 0xffffffffu) return BGN_OK;
-      req.key.w_in[k] = (uint32_t)ins[k].w;
-      req.in[k] = (const uint8_t*)ins[k].p;
-    }
-  for (int k = 0; k < 2; ++k)
-    if (outs[k].p) {
-      req.key.w_out[k] = (uint32_t)outs[k].w;
-      req.out[k] = (uint8_t*)const_cast<void*>(outs[k].p);
-    }
-  Combiner* cb = get_combiner(c);
-  if (!cb) return BGN_OK;
-  *taken = true;
-  int64_t cap = opt(c, &Options::combine_max_batch);
-  if (cap < (int64_t)count) cap = (int64_t)count;
-  std::string err;
-  const int rc = cb->submit(req, (size_t)cap, opt(c, &Options::combine_wait_us), opt(c, &Options::combine_regroup_pct), &err);
-  if (rc) return fail(rc, "%s", err.c_str());
-  return BGN_OK;
-}
-}  // namespace
 
 // ---- calibration of the batch-size crossovers ----------------------------------------------------------------------
 // The three pairing-kernel families have different shapes of time against batch size: the cooperative kernel is
