@@ -25,7 +25,7 @@
 #include "consts.hpp"
 #include "coop/coop_api.hpp"
 #include "quad/quad_api.hpp"
-#include "options.hpp"
+#include "dispatch.hpp"      // (and options.hpp)
 #include "combiner.hpp"
 
 using namespace bgn;
@@ -51,9 +51,6 @@ int fail(int code, const char* fmt, ...) {
   } while (0)
 
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// lane offsets inside a limb row are 32-bit byte offsets (gmem.hpp): at most 2^28 elements per call
-constexpr size_t kMaxBatch = (size_t)1 << 28;
 
 }  // namespace
 
@@ -82,20 +79,11 @@ struct HostPipeState {
   }
 };
 
-// Crossovers between the three pairing-kernel families, in elements per call; index = mode (0 Mult, 1 makeL2,
-// 2 Decrypt's lift, 3 Decrypt's power).  -1: the constants of the committed sweeps (coop_limit / quad_limit below);
-// bgn_ctx_calibrate replaces them by what two timed probes per kernel say on THIS device.
-// (atomics: bgn_ctx_calibrate publishes them while other threads' calls read them in their dispatch)
-struct Crossovers {
-  std::atomic<int64_t> coop[4] = {{-1}, {-1}, {-1}, {-1}};
-  std::atomic<int64_t> quad[4] = {{-1}, {-1}, {-1}, {-1}};
-};
-
 struct bgn_ctx {
   HostPipeState pipe;
   Options opt;                         // the knobs of this context (options.hpp): environment at creation, then
   Options opt_initial;                 // bgn_ctx_set_option; opt_initial: what bgn_ctx_reset_options goes back to
-  Crossovers xo;
+  Crossovers xo;                       // calibrated crossovers of the kernel families (dispatch.hpp)
   Combiner* comb = nullptr;            // combiner of concurrent small host-buffer calls
   int device = 0;
   int L = 0;          // bytes per F_p value on the wire
@@ -195,9 +183,13 @@ namespace {
 // probes are `_dev` calls made from that thread), never by rewriting the context's options under other callers.
 thread_local const bgn_ctx* g_opt_override_ctx = nullptr;
 thread_local const Options* g_opt_override = nullptr;
-inline int64_t opt(const bgn_ctx* c, Options::V Options::*f) {
-  if (g_opt_override_ctx == c && g_opt_override) return (g_opt_override->*f).load(std::memory_order_relaxed);
-  return (c->opt.*f).load(std::memory_order_relaxed);
+inline const Options* options_of(const bgn_ctx* c) { return (g_opt_override_ctx == c && g_opt_override) ? g_opt_override : &c->opt; }
+inline int64_t opt(const bgn_ctx* c, Options::V Options::*f) { return (options_of(c)->*f).load(std::memory_order_relaxed); }
+
+// What the kernel dispatch (dispatch.hpp) reads of a context (one limb per lane of a wave: no cooperative kernel beyond 64 limbs)
+DispatchView dispatch_view(const bgn_ctx* c) {
+  return DispatchView{c->nl, c->fixed_normalized && opt(c, &Options::coop_table) != 0, c->nl <= 64 && coop_ws_words(c->nl, 64) != 0,
+                      quad_ws_words(c->nl, 64) != 0, quad_g1_mul_ws_words(c->nl, 64, 1) != 0, options_of(c), &c->xo};
 }
 
 // Device memory of a context goes through these two: bgn_ctx_memory_bytes reports what it holds, and a budget
@@ -945,79 +937,14 @@ static int pairing_run(const bgn_ctx* c, size_t count) {
   return (int)r;
 }
 
-static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, const uint8_t* b, size_t nb, int mode,
-                         size_t d1, size_t d2, uint8_t* out, hipStream_t s, const uint8_t* r_be, size_t r_len,
-                         bool first_piece, bool last_piece);
-
-// Small batches go to the wave-cooperative kernel (coop/coop.hpp: one pairing per workgroup of eight waves) —
-// a lane of k_pairing runs a whole pairing alone, so any batch below one wave per SIMD (65536 pairings) costs
-// the latency of ONE pairing there (166 ms at a 1024-bit key, 28 ms at 512 bits), while the cooperative kernel
-// finishes a pairing in a few milliseconds and runs one per CU (several with more workgroups resident).
-// The crossovers come from the committed sweep profiles/r02_small_batch.csv; BGN_COOP_MAX / BGN_COOP_MAX_L2
-// override them (0 disables the kernel).
-static bool coop_table_walk(const bgn_ctx* c) { return c->fixed_normalized && opt(c, &Options::coop_table) != 0; }
-
-static size_t quad_limit(const bgn_ctx* c);
-
-static size_t coop_limit(const bgn_ctx* c, int mode) {
-  if (c->nl > 64) return 0;      // one limb per lane of a wave: no cooperative kernel beyond 64 limbs (2048-bit keys)
-  const int64_t ov = opt(c, mode >= 2 ? &Options::coop_max_dec : mode == 1 ? &Options::coop_max_l2 : &Options::coop_max);
-  if (ov >= 0) return (size_t)ov;
-  const bool tw = coop_table_walk(c);
-  // with the lane-group kernel's table walk and power above it (profiles/r03_mid_batch_table.csv, whole calls, 1024
-  // bits: Decrypt of 1024 ciphertexts 7.1 ms cooperative against 7.6, of 2048 12.3 against 7.6; makeL2 of 1024 7.9
-  // against 7.1 ms; 512 bits: Decrypt 1024: 2.1 against 1.9 ms, makeL2 1024: 2.7 against 2.1) the cooperative kernel
-  // keeps what is below that kernel's one-round time
-  const bool quad_tw = tw && quad_limit(c) != 0;
-  // mode 2: the lift of Decrypt.  The lane kernel walks the half-length table of the secret order (29 ms at 1024
-  // bits, 4.5 ms at 512, whatever the batch below 65536); the cooperative kernel walks the same table in two or
-  // three rounds per step (8192 lifts in 13 ms at 1024 bits, 8 ms at 512) — without the table walk it runs a whole
-  // e(C, P) and wins only below ~2000 / ~800 ciphertexts
-  if (quad_tw && c->xo.coop[mode] >= 0) return (size_t)c->xo.coop[mode];        // bgn_ctx_calibrate
-  if (mode == 2 || (mode == 3 && quad_tw)) {
-    if (quad_tw) return c->nl >= 36 ? 1300 : c->nl >= 19 ? 740 : 512;
-    return tw ? (c->nl >= 36 ? 14000 : c->nl >= 19 ? 4000 : 2048) : (c->nl >= 36 ? 2000 : c->nl >= 19 ? 800 : 512);
-  }
-  // mode 3: Decrypt's power by the secret key: 1.5 rounds per bit on the waves (≈ 1 ms at 1024 bits, one element
-  // per CU) against 2 products per bit on one lane (8 ms whatever the batch below 65536)
-  if (mode == 3) return c->nl >= 36 ? 2048 : c->nl >= 19 ? 1024 : 512;
-  // profiles/r02_small_batch.csv (MI355X): Mult at 1024 bits — 8192 pairings 114 ms cooperative against 166 ms,
-  // 16384: 225 against 166; at 512 bits — 4096: 17.1 against 28.2 ms, 8192: 33.0 against 28.2.  makeL2 (both
-  // kernels walk P's line table): 1024 bits — 8192: 52.5 against 54.3 ms, 16384: 103 against 54; 512 bits —
-  // 4096: 8.7 against 10.6 ms, 8192: 16.7 against 10.6 (general cooperative program: 3000 / 1800).
-  if (mode == 1) {
-    if (quad_tw) return c->nl >= 36 ? 850 : c->nl >= 19 ? 640 : 512;
-    return tw ? (c->nl >= 36 ? 8000 : c->nl >= 19 ? 4800 : 2048) : (c->nl >= 36 ? 3000 : c->nl >= 19 ? 1800 : 1024);
-  }
-  // Mult: with the lane-group kernel above it (profiles/r03_mid_batch.csv: 1024 pairs 17.8 ms cooperative against
-  // 21.2 ms, 1536: 25.1 against 21.3 at 1024 bits; 512 bits: 1024 pairs 5.3 against 5.2 ms) the crossover is where
-  // that kernel's one-round time is reached; without it, the lane kernel's (r02_small_batch.csv)
-  // (round 4, 24-instruction rows, nine-round segments and the width-5 loop: profiles/r04_mid_batch.csv 1024 pairs
-  // 17.0 ms cooperative against 16.0, 512 bits 5.3 against 4.5; profiles/r04_calibrate.csv puts the crossings at 950 / 815)
-  if (quad_limit(c)) return c->xo.coop[0] >= 0 ? (size_t)c->xo.coop[0] : c->nl >= 36 ? 950 : c->nl >= 19 ? 815 : 800;
-  return c->nl >= 36 ? 10000 : c->nl >= 19 ? 6000 : 4096;
+// The pairing workspace of one launch of `f` over a limb stride of sw elements: never less than the lane kernel's
+// (lane_slots F_p values per element), which is the fallback when a launcher refuses.
+static size_t pairing_ws_bytes(const bgn_ctx* c, Family f, size_t sw, int lane_slots, int qwin = 0) {
+  const size_t lane = (size_t)lane_slots * c->nl * sw * 4;
+  const size_t b = f == Family::Quad ? quad_ws_words(c->nl, sw, qwin) * 4 : f == Family::Coop ? coop_ws_words(c->nl, sw) * 4 : 0;
+  return b > lane ? b : lane;
 }
 
-// Between the cooperative kernel's saturation and one pairing per lane filling the chip sits the lane-group kernel
-// (quad/quad.hpp: sixteen lanes per pairing; 4096 pairings put one wave on every SIMD, three workgroups share a CU):
-// Mult and MultPoly's coefficient pairs above coop_limit and up to quad_limit pairs, from the committed sweep
-// profiles/r03_mid_batch.csv (MI355X, 1024 bits: 4096 pairs 18.9 ms, 16384 54.9 ms, 49152 153.3 ms against 155.5 ms
-// for ANY count up to 65536 on the lane kernel, 1024 pairs 21.2 ms against 17.8 ms cooperative; 512 bits: 4096
-// pairs 5.1 ms, 40960 27.9 ms against 28.2 ms, 1024 pairs 5.2 against 5.3 ms).  A lane of the lane kernel takes a
-// second pairing from 65537 pairs on: such a batch is cut into whole rounds of that kernel and a remainder that
-// comes back here (lane_rounds_head).  BGN_QUAD_MAX overrides the upper end (0 disables the kernel), BGN_QUAD_MIN
-// the lower one.
-static size_t quad_limit(const bgn_ctx* c) {
-  if (opt(c, &Options::quad_max) >= 0) return (size_t)opt(c, &Options::quad_max);
-  if (quad_ws_words(c->nl, 64) == 0) return 0;                        // no instantiation for this limb count
-  if (c->nl > 40) return kMaxBatch;     // 72 limbs: the lane kernels are the functional fallback, not the fast path
-  if (c->xo.quad[0] >= 0) return (size_t)c->xo.quad[0];                // bgn_ctx_calibrate
-  // profiles/r04_mid_batch.csv (nine-round segments, width-5 loop): 49152 pairs 128 ms, 65536 168 ms against 157 on the
-  // lane kernel (512 bits: 65536 pairs 36.1 against 28.6, 49152 27.7 against 28.5); profiles/r04_calibrate.csv: 61 600 / 50 900.
-  // Round 5: the lane kernel's round is 138 ms (lazy reduction), the lane groups are what they were — 49152 pairs
-  // 126 ms, 65536 167 ms (profiles/r05_mid_batch.csv); profiles/r05_calibrate.csv: 55 100 ... 55 400 / 45 500
-  return c->nl >= 36 ? 55000 : c->nl >= 19 ? 45500 : 32768;
-}
 // The lane-group pairing's Miller loop over the width-w NAF (quad.hpp k_pairing_quad_wtab: per-pairing table of the odd
 // multiples of A and their Miller values, 9 KB per pairing at 1024 bits): 9 % fewer rounds, two more table launches
 // and two more inversion launches.  Returns the width (0: the plain NAF).  Option quad_window: 0 never, 1 always.
@@ -1027,133 +954,6 @@ static int quad_window(const bgn_ctx* c, size_t count) {
   if (o == 0 || w < 3 || w > 5) return 0;
   if (o < 0 && quad_ws_words(c->nl, round_up(count, 64), w) * 4 > ((size_t)3 << 30)) return 0;
   return w;
-}
-
-// The walks over a key's line table (mode 1: makeL2; mode 2: Decrypt's lift) and Decrypt's power by the secret key
-// (mode 3) on the lane-group kernel: above the cooperative crossover of the same mode and up to these counts
-// (profiles/r03_mid_batch_table.csv); BGN_QUAD_MAX_L2 / BGN_QUAD_MAX_DEC / BGN_QUAD_MAX_POW override, 0 disables.
-static size_t quad_table_limit(const bgn_ctx* c, int mode) {
-  const int64_t ov = opt(c, mode == 3 ? &Options::quad_max_pow : mode == 2 ? &Options::quad_max_dec : &Options::quad_max_l2);
-  if (ov >= 0) return (size_t)ov;
-  if (quad_ws_words(c->nl, 64) == 0 || !quad_limit(c)) return 0;
-  if (c->nl > 40) return kMaxBatch;
-  if (c->xo.quad[mode] >= 0) return (size_t)c->xo.quad[mode];          // bgn_ctx_calibrate
-  // profiles/r03_mid_batch_table.csv, whole calls at 1024 / 512 bits: Decrypt of 16384 ciphertexts 21.0 / 4.3 ms
-  // against 36.6 / 6.9 on the lane kernels, of 32768 36.7 / 7.5 against 36.9 / 6.9; makeL2 of 32768 37.4 / 8.5 against
-  // 53.2 / 10.6, of 65536 72.2 / 15.9 against 53.7 / 10.8
-  // (round 4: profiles/r04_calibrate.csv 33 100 / 30 200 and 48 300 / 43 600; round 5, the table walks of the lane
-  // kernel with two sums of two products per step: profiles/r05_calibrate.csv 31 000 / 26 900 and 45 300 / 37 700)
-  if (mode == 3 || mode == 2) return c->nl >= 36 ? 31000 : c->nl >= 19 ? 26900 : 16384;
-  return c->nl >= 36 ? 45300 : c->nl >= 19 ? 37700 : 16384;
-}
-
-// MultConst with per-element scalars on the lane groups (quad/quad_g1.hpp: sixteen lanes per element, level 1 a
-// windowed Jacobian ladder, level 2 a windowed power in F_p^2): from ONE element on — there is no cooperative variant,
-// and a lone lane of k_g1_mul / k_gt_pow needs the latency of a whole ladder (96 ms for a 1024-bit scalar at a
-// 1024-bit key) — up to where one element per lane fills the chip better (profiles/r04_multconst_mid_batch.csv).
-// A larger batch is cut into whole rounds of 65536 lanes for the lane kernel and a remainder that comes back here.
-// Option quad_max_mc overrides (0: never).
-static size_t quad_mc_limit(const bgn_ctx* c, int level, size_t klen) {
-  const int64_t ov = opt(c, &Options::quad_max_mc);
-  if (ov >= 0) return (size_t)ov;
-  if (quad_g1_mul_ws_words(c->nl, 64, 1) == 0) return 0;             // no instantiation for this limb count
-  if (c->nl > 40) return kMaxBatch;                                   // 72 limbs: the lane kernels are the functional fallback
-  // profiles/r04_multconst_mid_batch.csv (MI355X, 1024-bit key, ms for 49152 / 65536 elements, lane groups against one
-  // element per lane): level 1, 1024-bit scalars 98 / 129 against 94 / 96; 256-bit 25.5 / 33.6 against 26.9 / 29.0;
-  // 40-bit (the lane kernel's binary ladder) 5.2 / 6.7 against 6.7 / 7.0.  Level 2: 1024-bit 35.7 / 47.0 against
-  // 35.5 / 35.6; 40-bit 2.1 / 2.7 against 1.5 / 1.5 (32768: 1.5 against 1.5).
-  // 512-bit key, 32768 / 49152 elements: level 1, 256-bit scalars 7.6 / 10.9 against 8.5 / 9.0, 40-bit 1.6 / 2.2 against
-  // 2.2 / 2.2; level 2, 256-bit 2.9 / 4.1 against 3.3 / 3.3, 40-bit 0.66 / 0.93 against 0.58 / 0.60.
-  const bool short_k = klen < 16;
-  // (round 4's 24-instruction rows, same file re-measured: level 1, 1024-bit scalars 49152 elements 96.0 against 93.7 ms;
-  // level 2 35.0 against 35.4)
-  // Round 6: on level 2 the lane kernel takes the norm-1 ladder (two products per scalar bit instead of five,
-  // kernels_impl.hpp k_gt_pow) and the lane groups still square and multiply, so the lane groups win a smaller range
-  // (profiles/r06_multconst_l2_crossover.csv: 1024-bit key, lane groups against lane kernel in ms,
-  // 16384 / 20480 elements: 1024-bit scalars 12.6 / 15.4 against 13.6; 256-bit 3.3 / 4.0 against 3.7; 40-bit 0.72 /
-  // 0.86 against 0.87 / 0.89.  512-bit key, 24576 / 32768: 256-bit 2.17 / 2.81 against 2.27; 40-bit 0.48 / 0.61
-  // against 0.48 / 0.50).
-  const bool ladder = level == 2 && opt(c, &Options::multconst_l2_ladder) != 0;
-  // Round 6, level 1 with short scalars: the lane kernel takes 2-bit windows from 3 scalar bytes on (g1_mul_launch) and
-  // is 1.3x the binary ladder it replaces (profiles/r06_multconst_short.csv: 1024-bit key, lane groups against lane
-  // kernel in ms at 49152 / 57344 elements: 40-bit 4.98 / 5.74 against 5.18; 64-bit 7.19 / 8.31 against 7.75; 120-bit
-  // 12.3 / 14.2 against 13.7; 8-bit (binary ladder) at 32768: 1.57 against 1.54.  512-bit key at 40960: 40-bit 1.82
-  // against 1.81, 120-bit 4.40 against 4.75; 8-bit at 16384 / 32768: 0.42 / 0.65 against 0.53).
-  const bool tiny_k = klen < 3;
-  const bool short_win = short_k && !tiny_k && opt(c, &Options::g1_mul_window_short) != 0;
-  if (c->nl >= 36)
-    return level == 1 ? (tiny_k ? 32768 : short_win ? 51000 : short_k ? 65536 : 47000)
-                      : ladder ? (short_k ? 21000 : 17500) : (short_k ? 32768 : 49000);
-  if (c->nl >= 19)
-    return level == 1 ? (tiny_k ? 24000 : short_win ? 41000 : short_k ? 48000 : 38000)
-                      : ladder ? (short_k ? 24000 : 26000) : (short_k ? 28000 : 37000);
-  return level == 1 ? 32768 : 24576;
-}
-
-static size_t quad_table_floor(const bgn_ctx* c, int mode) {
-  if (opt(c, &Options::quad_min) >= 0) return (size_t)opt(c, &Options::quad_min);
-  // an explicit cooperative limit alone keeps its A/B meaning (cooperative below it, lane kernel above)
-  if (opt(c, mode == 3 || mode == 2 ? &Options::coop_max_dec : &Options::coop_max_l2) >= 0 && opt(c, &Options::quad_max_l2) < 0 &&
-      opt(c, &Options::quad_max_dec) < 0 && opt(c, &Options::quad_max_pow) < 0)
-    return (size_t)-1;
-  return coop_limit(c, mode);
-}
-
-static bool use_quad(const bgn_ctx* c, size_t count, size_t coop_max) {
-  size_t lo = coop_max;
-  if (opt(c, &Options::quad_min) >= 0) lo = (size_t)opt(c, &Options::quad_min);
-  // coop_max alone keeps the meaning it had before this kernel existed (the A/B switch between the cooperative
-  // and the lane kernel: 0 = lane kernel always)
-  if (opt(c, &Options::coop_max) >= 0 && opt(c, &Options::quad_max) < 0 && opt(c, &Options::quad_min) < 0) return false;
-  const size_t hi = quad_limit(c);
-  if (!hi || count <= lo || quad_ws_words(c->nl, 64) == 0) return false;
-  return count <= hi;      // (a batch just above 65536 is cut into lane-kernel rounds and a remainder: lane_rounds_head)
-}
-
-// The lane kernel runs `pairing_run` pairings on each of at most 65536 lanes — one wave per SIMD, 512 registers — so
-// its time is a step function of the count: 65537 pairs cost two pairings' latency, 2^20 + 1 pairs two rounds of
-// sixteen.  A batch that does not fill whole rounds is therefore cut: the largest head that does (a multiple of
-// 2^20 above 2^20, of 65536 below) goes first, the remainder follows as a call of its own and takes whichever
-// kernel is fastest at ITS size (1024 bits: 70 000 Mults 310 -> 176 ms, 2^20 + 1000: 5.0 -> 2.5 s).  Below 2^20 the
-// cut is made only when the remainder lands on the cooperative or the lane-group kernel (a remainder on the lane
-// kernel costs the same extra round either way).  Element-wise modes only (Mult, makeL2).
-static size_t lane_rounds_head(const bgn_ctx* c, size_t n, int mode) {
-  constexpr size_t kLanes = 65536, kFull = kLanes * 16;
-  if (mode > 1 || n <= kLanes) return n;
-  if (opt(c, &Options::split_rounds) == 0) return n;
-  // (a batch the lane-group kernel takes whole — every size at 72 limbs — is not cut)
-  if (mode == 0 ? use_quad(c, n, coop_limit(c, 0))
-                : (coop_table_walk(c) && n > quad_table_floor(c, 1) && n <= quad_table_limit(c, 1)))
-    return n;
-  if (n > kFull) return n % kFull ? n - n % kFull : n;
-  const size_t rem = n % kLanes;
-  if (!rem) return n;
-  const bool small = mode == 0 ? (rem <= coop_limit(c, 0) || use_quad(c, rem, coop_limit(c, 0)))
-                               : (coop_table_walk(c) && (rem <= coop_limit(c, 1) || rem <= quad_table_limit(c, 1)));
-  return small ? n - rem : n;
-}
-
-// Mult / makeL2 over `count` pairs, in pieces of at most 2^22: the workspace of a piece (7.4 KB per pairing with
-// the width-5 loop) stays at 31 GB however long the arrays are.
-static int pairing_common(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, const uint8_t* b, size_t nb, int mode,
-                          size_t d1, size_t d2, uint8_t* out, hipStream_t s, const uint8_t* r_be = nullptr,
-                          size_t r_len = 0) {
-  if (!count) return BGN_OK;
-  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
-  const size_t piece = (size_t)1 << 22, eb = (size_t)2 * c->L;
-  for (size_t off = 0; off < count;) {
-    size_t n = count - off < piece ? count - off : piece;
-    n = lane_rounds_head(c, n, mode);
-    // the measurement hooks span the whole call: first event on the head piece, second on the last one; the kernel
-    // reported is the head piece's (it does nearly all the work of a batch cut into rounds + remainder)
-    int rc = pairing_chunk(c, n, a + off * eb, n, b ? b + off * eb : nullptr, b ? n : 0, mode, d1, d2, out + off * eb, s,
-                           r_be ? r_be + off * r_len : nullptr, r_len, off == 0, off + n >= count);
-    if (rc) return rc;
-    off += n;
-  }
-  (void)na;
-  (void)nb;
-  return BGN_OK;
 }
 
 static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, const uint8_t* b, size_t nb, int mode,
@@ -1172,15 +972,12 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
   probe.soa(c->nl, sa, true);
   if (nb) probe.soa(c->nl, sb, true);
   probe.soa(c->nl, so, false);
-  // makeL2 of a mid-size batch walks the key's normalised line table on the lane-group kernel
-  const bool quad_tab = mode == 1 && coop_table_walk(c) && count > quad_table_floor(c, 1) && count <= quad_table_limit(c, 1);
-  const bool quad = quad_tab || (mode == 0 && use_quad(c, count, coop_limit(c, 0)));
-  const bool coop = !quad && mode <= 1 && count <= coop_limit(c, mode);
-  const size_t lane_ws = (size_t)(mode == 1 ? 3 : c->pair_ws_slots) * c->nl * so * 4;
-  // (never less than the lane kernel's workspace: it is the fallback when a launcher has no instantiation)
-  const int qwin = (quad && !quad_tab) ? quad_window(c, count) : 0;
-  const size_t small_ws = quad ? quad_ws_words(c->nl, so, qwin) * 4 : coop ? coop_ws_words(c->nl, so) * 4 : 0;
-  const size_t ws_bytes = small_ws > lane_ws ? small_ws : lane_ws;
+  const DispatchView dv = dispatch_view(c);
+  const Family fam = family(dv, (Work)mode, count);
+  // makeL2 on the lane groups (a mid-size batch) walks the key's normalised line table
+  const bool quad_tab = fam == Family::Quad && mode == 1;
+  const int qwin = (fam == Family::Quad && !quad_tab) ? quad_window(c, count) : 0;
+  const size_t ws_bytes = pairing_ws_bytes(c, fam, so, mode == 1 ? 3 : c->pair_ws_slots, qwin);
   probe.take(ws_bytes);
   if (r_be) {
     probe.soa(c->nl, so, false);
@@ -1206,12 +1003,12 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
   const bool cf = opt(c, &Options::coop_fermat) == 1;
   // makeL2 on the waves walks the key's normalised line table (6 / 4 products per step in 2 / 3 rounds instead of
   // a full pairing's 18 / 36 in 3 / 6); BGN_COOP_TABLE=0 keeps the general program
-  const uint32_t* ctab = (mode == 1 && coop_table_walk(c)) ? c->d_fixedpair : nullptr;
-  if (quad && quad_pairing_launch(c->nl, s, c->d_params, c->d_consts, A, B, O, count, mode, 0, 0, ws, so, c->p_bits + 1,
+  const uint32_t* ctab = (mode == 1 && dv.table_walk) ? c->d_fixedpair : nullptr;
+  if (fam == Family::Quad && quad_pairing_launch(c->nl, s, c->d_params, c->d_consts, A, B, O, count, mode, 0, 0, ws, so, c->p_bits + 1,
                                   quad_tab ? c->d_fixedpair : nullptr, qwin)) {
     kname = quad_pairing_kernel_name(c->nl);
-  } else if (coop && coop_pairing_launch(c->nl, s, c->d_params, c->d_consts, A, B, O, count, mode, 0, 0,
-                                         cf ? nullptr : ws, so, c->p_bits + 1, ctab)) {
+  } else if (fam == Family::Coop && coop_pairing_launch(c->nl, s, c->d_params, c->d_consts, A, B, O, count, mode, 0, 0,
+                                                        cf ? nullptr : ws, so, c->p_bits + 1, ctab)) {
     kname = coop_pairing_kernel_name(c->nl);
   } else {
     kt->pairing(s, c->d_params, c->d_consts, A, B, O, count, mode, d1, d2, pairing_run(c, count), ws, so,
@@ -1229,16 +1026,36 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
   return BGN_OK;
 }
 
+// Mult / makeL2 over `count` pairs, in pieces of at most 2^22: the workspace of a piece (7.4 KB per pairing with
+// the width-5 loop) stays at 31 GB however long the arrays are.
+static int pairing_common(bgn_ctx* c, size_t count, const uint8_t* a, const uint8_t* b, int mode, size_t d1, size_t d2,
+                          uint8_t* out, hipStream_t s, const uint8_t* r_be = nullptr, size_t r_len = 0) {
+  if (!count) return BGN_OK;
+  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  const size_t piece = (size_t)1 << 22, eb = (size_t)2 * c->L;
+  for (size_t off = 0; off < count;) {
+    size_t n = count - off < piece ? count - off : piece;
+    n = rounds_head(dispatch_view(c), (Work)mode, n);      // whole rounds of the lane kernel first (dispatch.hpp)
+    // the measurement hooks span the whole call: first event on the head piece, second on the last one; the kernel
+    // reported is the head piece's (it does nearly all the work of a batch cut into rounds + remainder)
+    int rc = pairing_chunk(c, n, a + off * eb, n, b ? b + off * eb : nullptr, b ? n : 0, mode, d1, d2, out + off * eb, s,
+                           r_be ? r_be + off * r_len : nullptr, r_len, off == 0, off + n >= count);
+    if (rc) return rc;
+    off += n;
+  }
+  return BGN_OK;
+}
+
 int bgn_mult_batch_dev(bgn_ctx* c, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be, size_t r_len,
                        uint8_t* out, void* stream) {
   if (!c || (count && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
   if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
-  return pairing_common(c, count, a, count, b, count, 0, 0, 0, out, (hipStream_t)stream, r_be, r_len);
+  return pairing_common(c, count, a, b, 0, 0, 0, out, (hipStream_t)stream, r_be, r_len);
 }
 
 int bgn_make_l2_batch_dev(bgn_ctx* c, size_t count, const uint8_t* a, uint8_t* out, void* stream) {
   if (!c || (count && (!a || !out))) return fail(BGN_E_ARG, "null argument");
-  return pairing_common(c, count, a, count, nullptr, 0, 1, 0, 0, out, (hipStream_t)stream);
+  return pairing_common(c, count, a, nullptr, 1, 0, 0, out, (hipStream_t)stream);
 }
 
 // ---- Add / Sub / Neg / MultConst / Encrypt ------------------------------------------------
@@ -1888,8 +1705,8 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
     if (rc) return rc;
   }
   const size_t st = round_up(count, 64);
-  // the lane groups take up to quad_mc_limit elements (a whole small batch, or the remainder of a large one)
-  const size_t qlim = k_len <= 1024 ? quad_mc_limit(c, level, k_len) : 0;
+  // the lane groups take up to this many elements (a whole small batch, or the remainder of a large one)
+  const size_t qlim = k_len <= 1024 ? multconst_quad_limit(dispatch_view(c), level, k_len) : 0;
   // (where the lane groups take every size — 72 limbs — they take it in pieces of 2^17 elements, ten times what fills the
   // chip: the ladder's per-element table is 11.5 KB there, and the workspace stays 1.5 GB whatever the batch)
   const size_t qpiece = qlim > ((size_t)1 << 17) ? (size_t)1 << 17 : qlim;
@@ -2602,48 +2419,6 @@ int bgn_check_plaintext_knowledge_batch(bgn_ctx* c, size_t count, const uint8_t*
 
 // ---- Decrypt ---------------------------------------------------------------------------------
 static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct, int64_t* m, uint8_t* status, void* stream,
-                         bool first_piece, bool last_piece);
-
-// The level-1 lift runs on the lane kernel like Mult: whole rounds of it first, the remainder as a piece of its own
-// on whichever kernel is fastest at its size (lane_rounds_head).
-static size_t decrypt_rounds_head(const bgn_ctx* c, size_t n, int level) {
-  constexpr size_t kLanes = 65536, kFull = kLanes * 16;
-  if (n <= kLanes) return n;
-  if (opt(c, &Options::split_rounds) == 0) return n;
-  if (level == 2) {
-    // the power by the secret key: one element per lane, rounds of 65536; the cooperative and the lane-group kernel
-    // take a remainder in their ranges (1024 bits: 66 000 level-2 Decrypts 21.4 -> 13 ms)
-    const size_t rem = n % kLanes;
-    if (n > quad_table_floor(c, 3) && n <= quad_table_limit(c, 3)) return n;
-    return (rem && (rem <= coop_limit(c, 3) || rem <= quad_table_limit(c, 3))) ? n - rem : n;
-  }
-  const bool tw = coop_table_walk(c);
-  if (tw && n > quad_table_floor(c, 2) && n <= quad_table_limit(c, 2)) return n;      // the lane groups take it whole
-  if (n > kFull) return n % kFull ? n - n % kFull : n;
-  const size_t rem = n % kLanes;
-  if (!rem) return n;
-  return (rem <= coop_limit(c, 2) || (tw && rem <= quad_table_limit(c, 2))) ? n - rem : n;
-}
-
-int bgn_decrypt_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* ct, int64_t* m, uint8_t* status,
-                          void* stream) {
-  if (!c || (count && (!ct || !m || !status))) return fail(BGN_E_ARG, "null argument");
-  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
-  if (!c->have_secret) return fail(BGN_E_STATE, "secret key not set");
-  if (!c->have_tables) return fail(BGN_E_STATE, "DL tables not computed!");          // gsbs.go:56-58 (panic)
-  if (!count) return BGN_OK;
-  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
-  const size_t eb = (size_t)2 * c->L;
-  for (size_t off = 0; off < count;) {
-    const size_t n = decrypt_rounds_head(c, count - off, level);
-    int rc = decrypt_piece(c, n, level, ct + off * eb, m + off, status + off, stream, off == 0, off + n >= count);
-    if (rc) return rc;
-    off += n;
-  }
-  return BGN_OK;
-}
-
-static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct, int64_t* m, uint8_t* status, void* stream,
                          bool first_piece, bool last_piece) {
   hipStream_t s = (hipStream_t)stream;
   std::lock_guard<std::mutex> lk(c->mu);
@@ -2657,16 +2432,14 @@ static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct,
   uint32_t* todo = nullptr;
   uint32_t* todo_count = nullptr;
   uint32_t* pws = nullptr;
+  const DispatchView dv = dispatch_view(c);
+  const Family lift = family(dv, Work::Lift, count);
   for (int pass = 0; pass < 2; ++pass) {
     Ws w(c, pass ? c->arena : nullptr);
     A = (level == 1) ? w.g1(st) : w.gt(st);
     X = w.gt(st);
     Y = w.gt(st);
-    if (level == 1) {
-      const size_t lane_b = (size_t)3 * c->nl * st * 4, coop_b = coop_ws_words(c->nl, st) * 4, quad_b = quad_ws_words(c->nl, st) * 4;
-      const size_t small_b = coop_b > quad_b ? coop_b : quad_b;
-      pws = (uint32_t*)w.cv.take(count <= quad_table_limit(c, 2) || count <= coop_limit(c, 2) ? (small_b > lane_b ? small_b : lane_b) : lane_b);
-    }
+    if (level == 1) pws = (uint32_t*)w.cv.take(pairing_ws_bytes(c, lift, st, 3));
     todo = (uint32_t*)w.cv.take(st * 4);
     todo_count = (uint32_t*)w.cv.take(256);
     if (!pass) {
@@ -2686,13 +2459,13 @@ static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct,
     // a small batch lifts with the wave-cooperative kernel over the same line table (two or three rounds of products
     // per step instead of a whole table loop on a single lane: 28 ms at a 1024-bit key); the power by q1 below
     // gives the same e(C, P)^q1 whichever scalar the loop ran over
-    const bool ctab = coop_table_walk(c);                            // the table walk, over q2 when its table exists
+    const bool ctab = dv.table_walk;                                 // the table walk, over q2 when its table exists
     // ... and a mid-size batch with the lane-group kernel (sixteen lanes per lift, two or three rounds per step)
-    if (ctab && count > quad_table_floor(c, 2) && count <= quad_table_limit(c, 2) &&
+    if (lift == Family::Quad &&
         quad_pairing_launch(c->nl, s, c->d_params, sk_tab ? c->d_consts_sk : c->d_consts, A, c->key_P(), X, count, 1, 0, 0, pws,
                             st, c->p_bits + 1, sk_tab ? c->d_fixedpair_sk : c->d_fixedpair)) {
       aname = quad_pairing_kernel_name(c->nl);
-    } else if (count <= coop_limit(c, 2) &&
+    } else if (lift == Family::Coop &&
         coop_pairing_launch(c->nl, s, c->d_params, (ctab && sk_tab) ? c->d_consts_sk : c->d_consts, A, c->key_P(), X, count, 1,
                             0, 0, pws, st, c->p_bits + 1, ctab ? (sk_tab ? c->d_fixedpair_sk : c->d_fixedpair) : nullptr)) {
       aname = coop_pairing_kernel_name(c->nl);
@@ -2712,14 +2485,15 @@ static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct,
   // csk.PowBig(ct.C, sk.Key), bgn.go:223.  Level-2 ciphertexts and the lift both have norm 1: the power runs
   // on the real part (two products per bit).  BGN_DECRYPT_LUCAS=0 selects square-and-multiply in F_p^2.
   {
+    const Family pow = family(dv, Work::Power, count);
     if (opt(c, &Options::decrypt_lucas) == 0) {
       gt_pow_launch(c, s, base, c->d_sk, 0, c->sk_len, Y, count);
       kt->to_mont(s, c->d_params, Y.c0, Y.c1, Y.stride, count);
-    } else if (count > quad_table_floor(c, 3) && count <= quad_table_limit(c, 3) &&
+    } else if (pow == Family::Quad &&
                quad_gt_pow_launch(c->nl, s, c->d_params, base.c0, base.c1, base.stride, c->d_sk, c->sk_len, Y.c0, Y.c1, Y.stride,
                                   count)) {
       // a mid-size batch: the same square-and-multiply on the lane groups, sixteen lanes per element
-    } else if (count <= coop_limit(c, 3) &&
+    } else if (pow == Family::Coop &&
                coop_gt_pow_launch(c->nl, s, c->d_params, base.c0, base.c1, base.stride, c->d_sk, 0, c->sk_len, Y.c0, Y.c1,
                                   Y.stride, count)) {
       // a small batch: square-and-multiply on the waves (0.9 ms at a 1024-bit key) instead of 8 ms on one lane
@@ -2748,6 +2522,25 @@ static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct,
     c->last_kernel = kt->bsgs_kernel_name;
   }
   HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+
+int bgn_decrypt_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* ct, int64_t* m, uint8_t* status,
+                          void* stream) {
+  if (!c || (count && (!ct || !m || !status))) return fail(BGN_E_ARG, "null argument");
+  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
+  if (!c->have_secret) return fail(BGN_E_STATE, "secret key not set");
+  if (!c->have_tables) return fail(BGN_E_STATE, "DL tables not computed!");          // gsbs.go:56-58 (panic)
+  if (!count) return BGN_OK;
+  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  const size_t eb = (size_t)2 * c->L;
+  for (size_t off = 0; off < count;) {
+    // whole rounds of the lane kernel first, the remainder as a piece of its own on the kernel fastest at its size
+    const size_t n = rounds_head(dispatch_view(c), level == 1 ? Work::Lift : Work::Power, count - off);
+    int rc = decrypt_piece(c, n, level, ct + off * eb, m + off, status + off, stream, off == 0, off + n >= count);
+    if (rc) return rc;
+    off += n;
+  }
   return BGN_OK;
 }
 
@@ -2817,8 +2610,8 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
   // MultPoly calls are ONE product of ~10 x 10 coefficients) pairs directly, one pair per workgroup: tables and the
   // one-pairing-per-lane kernels cost the latency of several whole pairings on single lanes
   const size_t total_pairs = npoly * d1 * d2;
-  const bool quad = use_quad(c, total_pairs, coop_limit(c, 0));
-  const bool coop = !quad && total_pairs <= coop_limit(c, 0);
+  const DispatchView dv = dispatch_view(c);
+  const Family fam = family(dv, Work::Mult, total_pairs);
   // Up to 65536 pairs the lane kernel pairs directly in ONE pairing's latency; a table round costs a table build (as
   // long as a pairing) plus the walks (1024 bits, 512 products of 16 x 16: 195 ms with tables).
   size_t kLanes = 65536;
@@ -2831,7 +2624,7 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
   // layout (whole groups of 64 products) and says when the budget cannot take it.
   bool multi = d1 == d2 && d1 >= 2 && opt(c, &Options::poly_multi) != 0;
   size_t chunk = 0;                                           // polynomials per pass; 0: direct
-  if ((forced || (!coop && !quad && !one_round)) && d1 * d2 >= 2) chunk = poly_table_chunk(c, npoly, dt, &multi);
+  if ((forced || (fam == Family::Lane && !one_round)) && d1 * d2 >= 2) chunk = poly_table_chunk(c, npoly, dt, &multi);
   if (!chunk) multi = false;
   // One lane builds one table and runs for the whole kernel, so the time of the table path is a step function of the
   // table count (1213 products of 16 x 16 = 65502 tables: 260 ms, 1300: 450 ms).  Whole rounds of 65536 tables go
@@ -2851,8 +2644,9 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
   const size_t tail_pairs = tail_polys * d1 * d2;
   const bool tail_direct = tail_pairs != 0 && tail_pairs <= kLanes;
   const size_t tail_sp = round_up(tail_pairs ? tail_pairs : 1, 64);
+  const Family tail_fam = tail_direct ? family(dv, Work::Mult, tail_pairs) : Family::Lane;
   // (the width-w loop of the lane-group kernel is decided once per stride: the workspace below is sized with it)
-  const int qwin_main = quad ? quad_window(c, np) : 0, qwin_tail = tail_direct ? quad_window(c, tail_pairs) : 0;
+  const int qwin_main = fam == Family::Quad ? quad_window(c, np) : 0, qwin_tail = tail_fam == Family::Quad ? quad_window(c, tail_pairs) : 0;
   SoA2 E, Tt, Vt;
   uint32_t* pws = nullptr;
   for (int pass = 0; pass < 2; ++pass) {
@@ -2862,15 +2656,8 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
       Tt = w.g1(d1 * Qp);
       Vt = w.g1(d1 * Qp);
     }
-    size_t ws_b = (size_t)(chunk ? 3 : c->pair_ws_slots) * c->nl * sp * 4;         // the lane kernel is the fallback
-    auto at_least = [&](size_t b) { if (b > ws_b) ws_b = b; };
-    if (quad) at_least(quad_ws_words(c->nl, sp, qwin_main) * 4);
-    if (coop) at_least(coop_ws_words(c->nl, sp) * 4);
-    if (tail_direct) {
-      at_least((size_t)c->pair_ws_slots * c->nl * tail_sp * 4);
-      at_least(quad_ws_words(c->nl, tail_sp, qwin_tail) * 4);
-      at_least(coop_ws_words(c->nl, tail_sp) * 4);
-    }
+    size_t ws_b = pairing_ws_bytes(c, fam, sp, chunk ? 3 : c->pair_ws_slots, qwin_main);
+    if (tail_direct) ws_b = std::max(ws_b, pairing_ws_bytes(c, tail_fam, tail_sp, c->pair_ws_slots, qwin_tail));
     pws = (uint32_t*)w.cv.take(ws_b);
     if (!pass) {
       int rc = ensure_arena(c, w.cv.off);
@@ -2904,8 +2691,7 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
     const bool tail = tail_direct && nq == tail_polys && q0 + nq == npoly;        // the remainder after the whole rounds
     const bool direct = !chunk || tail;
     const size_t sw = tail ? tail_sp : sp;
-    const bool q_quad = tail ? use_quad(c, pairs, coop_limit(c, 0)) : quad;
-    const bool q_coop = tail ? (!q_quad && pairs <= coop_limit(c, 0)) : coop;
+    const Family q_fam = tail ? tail_fam : fam;      // (the tail has tail_pairs pairs)
     if (!direct && multi) {
       const size_t Qq = round_up(nq, 64);                                          // (the last chunk may be shorter)
       kt->soa_coeff_major(s, Aq, Tt, nq, d1, Qq);
@@ -2929,10 +2715,10 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
       kt->pairing(s, c->d_params, c->d_consts, V, T, E, pairs, tab_on_a ? 3 : 4, d1, d2, pairing_run(c, pairs), pws, sp,
                   tab, ts, 0);                                                     // pk.Mult(coeff1, coeff2), poly.go:146
       if (!tables_used) tables_used = 1;
-    } else if (q_quad && quad_pairing_launch(c->nl, s, c->d_params, c->d_consts, Aq, Bq, E, pairs, 2, d1, d2, pws, sw,
+    } else if (q_fam == Family::Quad && quad_pairing_launch(c->nl, s, c->d_params, c->d_consts, Aq, Bq, E, pairs, 2, d1, d2, pws, sw,
                                              c->p_bits + 1, nullptr, tail ? qwin_tail : qwin_main)) {
       c->last_kernel = quad_pairing_kernel_name(c->nl);
-    } else if (q_coop && coop_pairing_launch(c->nl, s, c->d_params, c->d_consts, Aq, Bq, E, pairs, 2, d1, d2, pws, sw,
+    } else if (q_fam == Family::Coop && coop_pairing_launch(c->nl, s, c->d_params, c->d_consts, Aq, Bq, E, pairs, 2, d1, d2, pws, sw,
                                              c->p_bits + 1)) {
       c->last_kernel = coop_pairing_kernel_name(c->nl);
     } else {
@@ -2971,10 +2757,11 @@ static int poly_plan_levels(const bgn_ctx* c, size_t npoly, size_t d, int max_le
   if (max_levels == 0) return 0;
   const double B = 129, W = 65, D = 160, kLanes = 65536.0;            // ms at 1024 bits; only the ratios matter
   const double quad_pair = 3.44e-3, quad_floor = 19, coop_pair = 14.5e-3, coop_floor = 6.8;
-  const size_t coop_max = coop_limit(c, 0);
+  const DispatchView dv = dispatch_view(c);
   auto direct = [&](double pairs) {                      // one launch of the kernel poly_mult_core picks for `pairs`
-    if (pairs <= (double)coop_max) return coop_floor > pairs * coop_pair ? coop_floor : pairs * coop_pair;
-    if (use_quad(c, (size_t)pairs, coop_max)) return quad_floor > pairs * quad_pair ? quad_floor : pairs * quad_pair;
+    const Family f = family(dv, Work::Mult, (size_t)pairs);
+    if (f == Family::Coop) return coop_floor > pairs * coop_pair ? coop_floor : pairs * coop_pair;
+    if (f == Family::Quad) return quad_floor > pairs * quad_pair ? quad_floor : pairs * quad_pair;
     return D * __builtin_ceil(pairs / kLanes);
   };
   int best = 0;

@@ -272,7 +272,7 @@ def test_table_walks_and_decrypt_agree_across_kernels_on_large_batches(name, cou
 
 def test_batches_that_do_not_fill_lane_kernel_rounds_are_cut(engopts):
     """65536 + r elements: the engine runs whole rounds of the lane kernel and hands the remainder to the kernel that
-    is fastest at ITS size (engine.cpp lane_rounds_head / decrypt_rounds_head).  Same bytes / plaintexts as the single
+    is fastest at ITS size (dispatch.hpp rounds_head).  Same bytes / plaintexts as the single
     launch (option split_rounds = 0), for Mult, makeL2 and level-1 Decrypt.  The kernel the measurement hooks report is
     the HEAD piece's (the lane kernel either way: it does nearly all the work), so the cut shows in the time: one round
     of the lane kernel + a short launch instead of two rounds."""

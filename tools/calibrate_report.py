@@ -13,7 +13,7 @@ import torch  # noqa: E402,F401
 from conftest import load_fixture  # noqa: E402
 import bgn_amd  # noqa: E402
 
-COMMITTED = {   # engine.cpp coop_limit / quad_limit / quad_table_limit (profiles/r04_mid_batch*.csv)
+COMMITTED = {   # dispatch.hpp coop_limit / quad_max (profiles/r04_mid_batch*.csv)
     "k1024": {"coop": [950, 850, 1300, 1300], "quad": [55000, 45300, 31000, 31000]},
     "k512": {"coop": [815, 640, 740, 740], "quad": [45500, 37700, 26900, 26900]},
 }

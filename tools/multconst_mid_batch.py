@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """MultConst (per-element scalars, bgn.go:253-291) by batch size: the lane groups (quad/quad_g1.hpp) against one element
-per lane, both levels, device-resident operands, best of three; the crossover of engine.cpp quad_mc_limit comes from
+per lane, both levels, device-resident operands, best of three; the crossover of dispatch.hpp multconst_quad_limit comes from
 this sweep.    python tools/multconst_mid_batch.py [k1024 ...] > profiles/r04_multconst_mid_batch.csv"""
 import os
 import sys

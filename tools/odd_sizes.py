@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Batch sizes that do not fill whole rounds of the lane kernel (65536 lanes, up to sixteen pairings each): wall
 time of Mult, makeL2 and Decrypt of both levels under the default dispatch with the cut into whole rounds + remainder
-(engine.cpp lane_rounds_head / decrypt_rounds_head) and without it (BGN_SPLIT_ROUNDS=0); device-resident operands,
+(dispatch.hpp rounds_head) and without it (BGN_SPLIT_ROUNDS=0); device-resident operands,
 best of three, results of the two compared.
     python tools/odd_sizes.py [k1024] > profiles/r03_odd_sizes.csv"""
 import os

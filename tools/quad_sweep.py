@@ -2,8 +2,8 @@
 """Mid-size batches: wall time by batch size on the three kernel families — the wave-cooperative one
 (coop/coop.hpp), the lane-group one (quad/quad.hpp) and one element per lane — device-resident operands, best of
 three, results compared.  Operations (QUAD_SWEEP_OPS, default "mult"): mult; make_l2 and decrypt_l1 (walks over a
-key's line table; Decrypt also its power by the secret key).  The crossovers of coop_limit / quad_limit /
-quad_table_limit (engine.cpp) are chosen from these CSVs:
+key's line table; Decrypt also its power by the secret key).  The crossovers of coop_limit / quad_max
+(dispatch.hpp) are chosen from these CSVs:
     python tools/quad_sweep.py [k1024 ...] > profiles/r03_mid_batch.csv
     QUAD_SWEEP_OPS=make_l2,decrypt_l1 python tools/quad_sweep.py > profiles/r03_mid_batch_table.csv"""
 import os

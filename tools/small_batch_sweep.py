@@ -2,7 +2,7 @@
 """Small-batch sweep: Mult / makeL2 / level-1 Decrypt wall time by batch size on the wave-cooperative kernel
 (coop/coop.hpp; makeL2 and Decrypt's lift walk the key's line table there) and on the one-pairing-per-lane kernel,
 device-resident operands, best of three.  Writes the CSV the engine's crossovers
-(coop_limit, engine.cpp) are chosen from:  python tools/small_batch_sweep.py > profiles/r02_small_batch.csv"""
+(coop_limit, dispatch.hpp) are chosen from:  python tools/small_batch_sweep.py > profiles/r02_small_batch.csv"""
 import os
 import sys
 import time
