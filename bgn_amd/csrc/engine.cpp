@@ -124,6 +124,9 @@ struct bgn_ctx {
   uint32_t* d_fixedpair = nullptr;     // line table of e(P, .), 3 * nl u32 per Miller step (fixedpair.hpp)
   size_t miller_steps = 0;
   PairingConsts pc_host;               // host image of *d_consts
+  // Mult on the a = -3 curve (pairing.hpp miller_double): u^2 R^2 | u^3 R^2 mod p, 2 * nl tight limbs — the factors
+  // k_decode multiplies x and y by instead of R^2.  Null: p has no fourth root of -3, the route is off for this key.
+  uint32_t* d_a3 = nullptr;
   int pair_ws_slots = 3;               // F_p values of pairing workspace per pairing: 3 + the windowed loop's table
   // decryption lift over the secret order (set_secret): line table of f_{q2, q1*P} and the constants whose
   // NAF is that of q2 = n / q1 — half the Miller steps of e(P, .)
@@ -476,6 +479,7 @@ void bgn_ctx_destroy(bgn_ctx* c) {
   if (c->d_params) (void)ctx_free(c, c->d_params);
   if (c->d_barrett) (void)ctx_free(c, c->d_barrett);
   if (c->d_consts) (void)ctx_free(c, c->d_consts);
+  if (c->d_a3) (void)ctx_free(c, c->d_a3);
   if (c->d_keypts) (void)ctx_free(c, c->d_keypts);
   if (c->d_keywire) (void)ctx_free(c, c->d_keywire);
   if (c->d_sk) {
@@ -595,6 +599,24 @@ int bgn_ctx_create(bgn_ctx** out, const uint8_t* p_be, size_t p_len, const uint8
     HIP_BRK(ctx_malloc(c, (void**)&c->d_consts, sizeof pc));
     HIP_BRK(hipMemcpy(c->d_consts, &pc, sizeof pc, hipMemcpyHostToDevice));
     c->pc_host = pc;
+    {
+      // the decode factors of the a = -3 route (hostbig.hpp curve_a3_root): (x, y) -> (u^2 x, u^3 y), u^4 = -3
+      BigU u;
+      if (curve_a3_root(p, u)) {
+        const ModP F(p);
+        BigU r2dev((uint64_t)1);                           // R^2 mod p, R = 2^(LIMB_BITS * nl)
+        for (int i = 0; i < 2 * LIMB_BITS * c->nl; ++i) {
+          r2dev.shl1();
+          if (BigU::cmp(r2dev, p) >= 0) r2dev.sub(p);
+        }
+        const BigU fx = F.mul(F.mul(u, u), r2dev), fy = F.mul(fx, u);
+        std::vector<uint32_t> f((size_t)2 * c->nl);
+        fx.to_limbs(f.data(), c->nl, LIMB_BITS);
+        fy.to_limbs(f.data() + c->nl, c->nl, LIMB_BITS);
+        HIP_BRK(ctx_malloc(c, (void**)&c->d_a3, f.size() * 4));
+        HIP_BRK(hipMemcpy(c->d_a3, f.data(), f.size() * 4, hipMemcpyHostToDevice));
+      }
+    }
 
     // key points -> Montgomery SoA (stride 1)
     HIP_BRK(ctx_malloc(c, (void**)&c->d_keywire, (size_t)6 * c->L));
@@ -602,9 +624,9 @@ int bgn_ctx_create(bgn_ctx** out, const uint8_t* p_be, size_t p_len, const uint8
     HIP_BRK(hipMemcpy(c->d_keywire + 2 * c->L, Q_wire, (size_t)2 * c->L, hipMemcpyHostToDevice));
     HIP_BRK(ctx_malloc(c, (void**)&c->d_keypts, (size_t)8 * c->nl * 4));
     HIP_BRK(hipMemset(c->d_keypts, 0, (size_t)8 * c->nl * 4));
-    kt->decode(nullptr, c->d_params, c->d_keywire, c->L, 1, SoA2{c->d_keypts, c->d_keypts + c->nl, nullptr, 1});
+    kt->decode(nullptr, c->d_params, c->d_keywire, c->L, 1, SoA2{c->d_keypts, c->d_keypts + c->nl, nullptr, 1}, nullptr, nullptr);
     kt->decode(nullptr, c->d_params, c->d_keywire + 2 * c->L, c->L, 1,
-               SoA2{c->d_keypts + 2 * c->nl, c->d_keypts + 3 * c->nl, nullptr, 1});
+               SoA2{c->d_keypts + 2 * c->nl, c->d_keypts + 3 * c->nl, nullptr, 1}, nullptr, nullptr);
     // the GT identity; e(Q,Q), the blinding base of level-2 ops, is computed on first use (ensure_gt_table)
     HIP_BRK(hipMemcpy(c->d_keypts + 6 * c->nl, img.data() + c->nl, (size_t)c->nl * 4, hipMemcpyHostToDevice));  // one
     // line table of e(P, .) for makeL2 and the level-1 decryption lift (one lane, ~0.2 s per key)
@@ -724,6 +746,7 @@ int bgn_ctx_get_option(const bgn_ctx* c, const char* name, int64_t* value) {
   const OptionDesc* d = option_find(name);
   if (!d) return fail(BGN_E_ARG, "unknown option '%s'", name);
   *value = (c->opt.*(d->field)).load(std::memory_order_relaxed);
+  if (d->field == &Options::miller_a3) *value = (*value != 0 && c->d_a3) ? 1 : 0;      // whether the route is ACTIVE for this key
   return BGN_OK;
 }
 
@@ -995,8 +1018,15 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
     T1 = cv.soa(c->nl, so, false);
     T2 = cv.soa(c->nl, so, false);
   }
-  kt->decode(s, c->d_params, a, c->L, na, A);
-  if (nb) kt->decode(s, c->d_params, b, c->L, nb, B);
+  // Mult on the lane kernel runs on the a = -3 curve where the key admits it: A and B are then decoded through the
+  // isomorphism (u^2 R^2, u^3 R^2 in place of R^2).  Every other mode and kernel family works on a = 1.
+  const bool a3_ok = mode == 0 && nb && c->d_a3 && opt(c, &Options::miller_a3) != 0;
+  bool a3 = a3_ok && fam == Family::Lane;
+  auto decode_operands = [&] {
+    kt->decode(s, c->d_params, a, c->L, na, A, a3 ? c->d_a3 : nullptr, a3 ? c->d_a3 + c->nl : nullptr);
+    if (nb) kt->decode(s, c->d_params, b, c->L, nb, B, a3 ? c->d_a3 : nullptr, a3 ? c->d_a3 + c->nl : nullptr);
+  };
+  decode_operands();
   if (first_piece) HIP_TRY(hipEventRecord(c->ev0, s));
   const char* kname = "";
   // coop_fermat=1: the one-launch form with the Fermat inversion on the waves (A/B measurements)
@@ -1011,8 +1041,12 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
                                                         cf ? nullptr : ws, so, c->p_bits + 1, ctab)) {
     kname = coop_pairing_kernel_name(c->nl);
   } else {
+    if (a3_ok && !a3) {          // a lane-group or cooperative launcher refused: the lane kernel takes its own route
+      a3 = true;
+      decode_operands();
+    }
     kt->pairing(s, c->d_params, c->d_consts, A, B, O, count, mode, d1, d2, pairing_run(c, count), ws, so,
-                (mode == 1) ? c->d_fixedpair : nullptr, 1, (mode == 1) ? (c->fixed_normalized ? 2 : 0) : 0);
+                (mode == 1) ? c->d_fixedpair : nullptr, 1, (mode == 1) ? (c->fixed_normalized ? 2 : 0) : (a3 ? 4 : 0));
     kname = mode == 1 ? kt->pairing_table_kernel_name : kt->pairing_kernel_name;
   }
   if (first_piece) c->last_kernel = kname;
@@ -1618,7 +1652,7 @@ int addsub_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint
   } else {
     // wire-to-wire GT product: a stays plain, only b goes to Montgomery form (ops.hpp gt_mul_lane)
     kt->decode_plain(s, c->d_params, a, c->L, count, A);
-    kt->decode(s, c->d_params, b, c->L, count, B);
+    kt->decode(s, c->d_params, b, c->L, count, B, nullptr, nullptr);
   }
   HIP_TRY(hipEventRecord(c->ev0, s));
   if (level == 1) {
@@ -1731,7 +1765,7 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
     }
   }
   const KernelTable* kt = c->kt;
-  kt->decode(s, c->d_params, a, c->L, count, A);
+  kt->decode(s, c->d_params, a, c->L, count, A, nullptr, nullptr);
   auto view = [](SoA2 v, size_t off) {
     v.c0 += off;
     v.c1 += off;
@@ -2448,7 +2482,7 @@ static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct,
     }
   }
   const KernelTable* kt = c->kt;
-  kt->decode(s, c->d_params, ct, c->L, count, A);
+  kt->decode(s, c->d_params, ct, c->L, count, A, nullptr, nullptr);
   SoA2 base = A;
   if (level == 1) {
     // lift to GT: e(C, P) — the discrete log is the same (see bsgs.hpp).  With the secret-order table the
@@ -2840,8 +2874,8 @@ int bgn_poly_mult_batch_dev(bgn_ctx* c, size_t npoly, size_t d1, size_t d2, cons
       if (rc) return rc;
     }
   }
-  kt->decode(s, c->d_params, a, c->L, npoly * d1, A[0]);
-  kt->decode(s, c->d_params, b, c->L, npoly * d2, B[0]);
+  kt->decode(s, c->d_params, a, c->L, npoly * d1, A[0], nullptr, nullptr);
+  kt->decode(s, c->d_params, b, c->L, npoly * d2, B[0], nullptr, nullptr);
   HIP_TRY(hipEventRecord(c->ev0, s));
   for (int k = 0; k < levels; ++k) {
     for (int side = 0; side < 2; ++side) {
@@ -2907,7 +2941,7 @@ int poly_lin_common(bgn_ctx* c, size_t npoly, size_t d, size_t dp, int level, co
     k_dev = kbuf;
   }
   const KernelTable* kt = c->kt;
-  kt->decode(s, c->d_params, ct, c->L, nin, A);
+  kt->decode(s, c->d_params, ct, c->L, nin, A, nullptr, nullptr);
   PolyLinArgs a;
   a.cx = A.c0; a.cy = A.c1; a.cinf = A.inf; a.sc = A.stride;
   a.k = k_dev; a.klen = k_len; a.kq = kq;

@@ -343,7 +343,8 @@ __device__ __forceinline__ void fp_neg(Fp<NL>& r, const Fp<NL>& a, const FpParam
 // coefficients (K = 0: no multiple of p).  The step programs of pairing.hpp use it where a chain of fp_dbl /
 // fp_add / fp_sub passes (three instructions per limb each) forms one value.  The VALUE must be non-negative and
 // below 2^(LIMB_BITS*NL) — the caller's bounds, as for fp_sub; per limb the positive part (coefficients > 0, plus
-// one for K*p) may reach 3 * 2^LIMB_BITS and so may the negative part: both fit an i32 with the carry.
+// one for K*p) may reach 3 * 2^LIMB_BITS and so may the negative part: both fit an i32 with the carry.  A
+// combination without a negative coefficient may reach 7 * 2^LIMB_BITS per limb: it is summed unsigned.
 template <int CA, int CB, int CC, int K, int NL>
 __device__ __forceinline__ void fp_lin3(Fp<NL>& r, const Fp<NL>& a, const Fp<NL>& b, const Fp<NL>& c3,
                                         const FpParams<NL>* __restrict__ P) {
@@ -351,19 +352,35 @@ __device__ __forceinline__ void fp_lin3(Fp<NL>& r, const Fp<NL>& a, const Fp<NL>
   static_assert(K >= 0 && K <= KP_MAX, "K*p table");
   constexpr int pos = (CA > 0 ? CA : 0) + (CB > 0 ? CB : 0) + (CC > 0 ? CC : 0) + (K > 0 ? 1 : 0);
   constexpr int neg = (CA < 0 ? -CA : 0) + (CB < 0 ? -CB : 0) + (CC < 0 ? -CC : 0);
-  static_assert(pos <= 3 && neg <= 3, "a limb of the combination must fit 32 bits");
-  i32 c = 0;
+  if constexpr (neg == 0 && pos > 3) {
+    static_assert(pos <= 7 && LIMB_BITS <= 29, "a limb of the combination must fit 32 bits");
+    u32 c = 0;
 #pragma unroll
-  for (int j = 0; j < NL; ++j) {
-    i32 s = c;
-    if (K > 0) s += (i32)P->kp[K > 0 ? K - 1 : 0][j];
-    if (CA != 0) s += CA * (i32)a.v[j];
-    if (CB != 0) s += CB * (i32)b.v[j];
-    if (CC != 0) s += CC * (i32)c3.v[j];
-    r.v[j] = (u32)s & LIMB_MASK;
-    c = s >> LIMB_BITS;
+    for (int j = 0; j < NL; ++j) {
+      u32 s = c;
+      if (K > 0) s += P->kp[K > 0 ? K - 1 : 0][j];
+      if (CA != 0) s += (u32)CA * a.v[j];
+      if (CB != 0) s += (u32)CB * b.v[j];
+      if (CC != 0) s += (u32)CC * c3.v[j];
+      r.v[j] = s & LIMB_MASK;
+      c = s >> LIMB_BITS;
+    }
+    BGN_CHECK(c == 0, "fp_lin: carry out of the top limb");
+  } else {
+    static_assert(pos <= 3 && neg <= 3, "a limb of the combination must fit 32 bits");
+    i32 c = 0;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      i32 s = c;
+      if (K > 0) s += (i32)P->kp[K > 0 ? K - 1 : 0][j];
+      if (CA != 0) s += CA * (i32)a.v[j];
+      if (CB != 0) s += CB * (i32)b.v[j];
+      if (CC != 0) s += CC * (i32)c3.v[j];
+      r.v[j] = (u32)s & LIMB_MASK;
+      c = s >> LIMB_BITS;
+    }
+    BGN_CHECK(c == 0, "fp_lin: negative value or carry out of the top limb");
   }
-  BGN_CHECK(c == 0, "fp_lin: negative value or carry out of the top limb");
 }
 template <int CA, int CB, int K, int NL>
 __device__ __forceinline__ void fp_lin2(Fp<NL>& r, const Fp<NL>& a, const Fp<NL>& b, const FpParams<NL>* __restrict__ P) {
@@ -925,6 +942,19 @@ __device__ __forceinline__ void fp_to_mont(Fp<NL>& r, const Fp<NL>& a, const FpP
   l_store<NL>(stage, a);
   Fp<NL> x;
   fp_mul<NL>(x, stage, r2, P);
+  fp_cond_sub_p<NL>(r, x, P);
+}
+
+// r = a*c*R mod p for a wave-uniform constant given as f = c*R^2 mod p (tight limbs, < p): the conversion to
+// Montgomery form with a scaling folded in, at the price of fp_to_mont (f = P->r2 is fp_to_mont).
+template <int NL>
+__device__ __forceinline__ void fp_to_mont_scaled(Fp<NL>& r, const Fp<NL>& a, const u32* __restrict__ f,
+                                                  const FpParams<NL>* __restrict__ P, LFp<NL>* stage) {
+  Fp<NL> c;
+  fp_set(c, f);
+  l_store<NL>(stage, a);
+  Fp<NL> x;
+  fp_mul<NL>(x, stage, c, P);
   fp_cond_sub_p<NL>(r, x, P);
 }
 

@@ -198,4 +198,100 @@ struct BigU {
   }
 };
 
+// Products and powers modulo an odd p (set-up only).  Values are plain residues below p; a product goes through
+// two word-serial Montgomery multiplications in base 2^32 (a*b/R, then * R^2/R).
+struct ModP {
+  BigU p;
+  size_t k = 0;                 // words of p
+  uint32_t ninv = 0;            // -p^{-1} mod 2^32
+  std::vector<uint32_t> r2;     // R^2 mod p, R = 2^(32 k)
+
+  explicit ModP(const BigU& modulus) : p(modulus), k(modulus.w.size()) {
+    uint32_t inv = 1;
+    for (int i = 0; i < 6; ++i) inv *= 2u - p.w[0] * inv;
+    ninv = 0u - inv;
+    BigU x((uint64_t)1);
+    for (size_t i = 0; i < 64 * k; ++i) {
+      x.shl1();
+      if (BigU::cmp(x, p) >= 0) x.sub(p);
+    }
+    r2 = words(x);
+  }
+  std::vector<uint32_t> words(const BigU& a) const {
+    std::vector<uint32_t> v(a.w);
+    v.resize(k, 0);
+    return v;
+  }
+  // a*b/R mod p on k-word operands below p
+  std::vector<uint32_t> mont(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b) const {
+    std::vector<uint32_t> t(k + 2, 0);
+    for (size_t i = 0; i < k; ++i) {
+      uint64_t c = 0;
+      for (size_t j = 0; j < k; ++j) {
+        c += (uint64_t)a[i] * b[j] + t[j];
+        t[j] = (uint32_t)c;
+        c >>= 32;
+      }
+      c += t[k];
+      t[k] = (uint32_t)c;
+      t[k + 1] = (uint32_t)(c >> 32);
+      const uint32_t m = t[0] * ninv;
+      c = ((uint64_t)m * p.w[0] + t[0]) >> 32;
+      for (size_t j = 1; j < k; ++j) {
+        c += (uint64_t)m * p.w[j] + t[j];
+        t[j - 1] = (uint32_t)c;
+        c >>= 32;
+      }
+      c += t[k];
+      t[k - 1] = (uint32_t)c;
+      t[k] = t[k + 1] + (uint32_t)(c >> 32);
+    }
+    BigU r;
+    r.w.assign(t.begin(), t.begin() + k + 1);
+    r.trim();
+    if (BigU::cmp(r, p) >= 0) r.sub(p);
+    return words(r);
+  }
+  BigU mul(const BigU& a, const BigU& b) const {
+    BigU r;
+    r.w = mont(mont(words(a), words(b)), r2);
+    r.trim();
+    return r;
+  }
+  BigU pow(const BigU& a, const BigU& e) const {
+    const std::vector<uint32_t> am = mont(words(a), r2);          // a*R
+    std::vector<uint32_t> acc = mont(words(BigU((uint64_t)1)), r2);
+    for (int i = e.bits() - 1; i >= 0; --i) {
+      acc = mont(acc, acc);
+      if (e.bit(i)) acc = mont(acc, am);
+    }
+    BigU r;
+    r.w = mont(acc, words(BigU((uint64_t)1)));
+    r.trim();
+    return r;
+  }
+};
+
+// u in F_p with u^4 = -3, for p = 3 mod 4: the isomorphism (x, y) -> (u^2 x, u^3 y) from y^2 = x^3 + x onto
+// y^2 = x^3 - 3x that the Miller loop of pairing.hpp can run on.  -3 is a square exactly when p = 1 mod 3; of its
+// two roots +-s one is a square again (-1 is not a square), and s^((p+1)/4) is a root of that one whichever of the
+// two s is.  False when p admits no such u (or is not 3 mod 4); the result is verified, not assumed.
+inline bool curve_a3_root(const BigU& p, BigU& u) {
+  if (p.bits() < 3 || (p.w[0] & 3u) != 3u) return false;
+  BigU q, r;
+  BigU::divmod(p, BigU((uint64_t)3), q, r);
+  if (BigU::cmp(r, BigU((uint64_t)1)) != 0) return false;
+  const ModP F(p);
+  BigU e = p;
+  e.add_small(1);
+  e.shr1();
+  e.shr1();                                  // (p + 1) / 4
+  BigU m3 = p;
+  m3.sub(BigU((uint64_t)3));                 // -3
+  const BigU s = F.pow(m3, e);
+  u = F.pow(s, e);
+  const BigU u2 = F.mul(u, u);
+  return BigU::cmp(F.mul(u2, u2), m3) == 0;
+}
+
 }  // namespace bgn

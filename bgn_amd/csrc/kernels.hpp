@@ -202,8 +202,10 @@ struct KernelTable {
   const char* pairing_kernel_name;
   const char* pairing_table_kernel_name;   // the mode-1 instantiation (walk over a key's line table)
 
-  // wire bytes (2L per element, big-endian) -> SoA, canonical Montgomery form.
-  void (*decode)(hipStream_t s, const void* params, const uint8_t* wire, int L, size_t count, SoA2 out);
+  // wire bytes (2L per element, big-endian) -> SoA, canonical Montgomery form.  fx / fy: null, or per-coordinate
+  // factors c*R^2 mod p on the device (nl tight limbs each): x and y are stored as c_x*x*R, c_y*y*R.
+  void (*decode)(hipStream_t s, const void* params, const uint8_t* wire, int L, size_t count, SoA2 out,
+                 const uint32_t* fx, const uint32_t* fy);
   // wire bytes -> SoA, canonical plain residues (no Montgomery conversion): operands of a plain_io addition.
   void (*decode_plain)(hipStream_t s, const void* params, const uint8_t* wire, int L, size_t count, SoA2 out);
   // ok[e] = 1 iff wire element e is a valid encoding for the level (range; on the curve / norm 1).
@@ -227,7 +229,8 @@ struct KernelTable {
   void (*pairing)(hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, SoA2 b, SoA2 out,
                   size_t count, int mode, size_t d1, size_t d2, int run, uint32_t* ws, size_t sw,
                   const uint32_t* fixed_tab, size_t tab_stride,
-                  int variant /* bit 1 with a key table: the table is normalised */);
+                  int variant /* bit 1 with a key table: the table is normalised; bit 2, general loop only: a and b
+                                 are decoded onto the a = -3 curve (pairing.hpp miller_double) */);
   // builds the line table of e(P, .) : 3*NL u32 per Miller step (px, py canonical Montgomery, stride 1)
   void (*fixedpair_build)(hipStream_t s, const void* params, const PairingConsts* consts, const uint32_t* px,
                           const uint32_t* py, uint32_t* tab);

@@ -20,9 +20,12 @@ constexpr int NL_ = BGN_NL;
 
 // PLAIN: limbs of the residues as they are (what EAdd / ESub work on) — no Montgomery conversion and therefore no
 // product slot in LDS, so two workgroups fit a CU and overlap their staging copies.
+// fx / fy (not PLAIN): per-coordinate factors c*R^2 mod p, NL tight limbs each — x and y come out as c_x*x*R and
+// c_y*y*R (the isomorphism onto the a = -3 curve folded into the conversion, pairing.hpp); null: R^2, plain Montgomery form.
 template <int NL, bool PLAIN>
 __global__ void __launch_bounds__(FP_BLOCK)
-k_decode(const FpParams<NL>* __restrict__ P, const uint8_t* __restrict__ wire, int L, size_t count, SoA2 out) {
+k_decode(const FpParams<NL>* __restrict__ P, const uint8_t* __restrict__ wire, int L, size_t count, SoA2 out,
+         const u32* __restrict__ fx, const u32* __restrict__ fy) {
   __shared__ WireStage<NL> ws;
   const size_t e0 = (size_t)blockIdx.x * FP_BLOCK;
   const size_t nel = (count - e0 < (size_t)FP_BLOCK) ? count - e0 : (size_t)FP_BLOCK;
@@ -47,9 +50,9 @@ k_decode(const FpParams<NL>* __restrict__ P, const uint8_t* __restrict__ wire, i
   } else {
     __shared__ LFp<NL> stage;
     Fp<NL> m;
-    fp_to_mont<NL>(m, x, P, &stage);
+    fp_to_mont_scaled<NL>(m, x, fx ? fx : P->r2, P, &stage);
     g_store<NL>(out.c0, out.stride, e, m);
-    fp_to_mont<NL>(m, y, P, &stage);
+    fp_to_mont_scaled<NL>(m, y, fy ? fy : P->r2, P, &stage);
     g_store<NL>(out.c1, out.stride, e, m);
   }
 }
@@ -178,11 +181,12 @@ __device__ __forceinline__ size_t pair_index(PairOperands& op, size_t e, int mod
 // peels 1/N(f_j) off and finishes the exponentiation.  ws: 3 F_p per element (F0, F1, prefix), plus 4 more
 // win_slots(w) for the windowed Miller loop of VARIANT 0: (3 + win_slots(w)) * NL * sw u32 in all.
 // VARIANT 0: inlined step programs (pairing.hpp); 1: key-constant first argument (fixedpair.hpp)
+// curve_a3 (VARIANT 0): a and b were decoded onto y^2 = x^3 - 3x and the doubling steps run there (miller_double).
 template <int NL, int VARIANT>
 __global__ void __launch_bounds__(FP_BLOCK)
 k_pairing(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, SoA2 a, SoA2 b, SoA2 out,
           size_t count, int mode, size_t d1, size_t d2, int run, u32* __restrict__ ws, size_t sw,
-          const u32* __restrict__ fixed_tab, size_t tab_stride, int tab_normalized) {
+          const u32* __restrict__ fixed_tab, size_t tab_stride, int tab_normalized, int curve_a3) {
   __shared__ LFp<NL> L[4];
   const size_t T = (size_t)gridDim.x * FP_BLOCK;
   const size_t t = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
@@ -193,6 +197,7 @@ k_pairing(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ 
   op.bx = b.c0;
   op.by = b.c1;
   op.sb = b.stride;
+  op.a3 = VARIANT == 0 ? curve_a3 : 0;
   u32* wF0 = ws;
   u32* wF1 = ws + (size_t)NL * sw;
   u32* wPf = ws + (size_t)2 * NL * sw;
@@ -211,9 +216,14 @@ k_pairing(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ 
     else if (ws && C->wnaf_len > 0) {
       // windowed loop; its per-pairing table (dA, f_d) lives behind the three run arrays of ws
       WinTab W{ws + (size_t)3 * NL * sw, sw, e};
-      miller_loop_w<NL>(S, L, op, W, C, P);
-    } else
-      miller_loop<NL>(S, L, op, C, P);
+      if (op.a3)                          // wave-uniform kernel argument: one specialised copy of the loop per curve
+        miller_loop_w<NL, 1>(S, L, op, W, C, P);
+      else
+        miller_loop_w<NL, 0>(S, L, op, W, C, P);
+    } else if (op.a3)
+      miller_loop<NL, 1>(S, L, op, C, P);
+    else
+      miller_loop<NL, 0>(S, L, op, C, P);
     if (run == 1) {
       bool ident = (a.inf && a.inf[op.ea]) || (b.inf && b.inf[op.eb]);
       Fp<NL> N, ninv, g0, g1, re, im;
@@ -790,16 +800,17 @@ k_poly_acc(const FpParams<NL>* __restrict__ P, PolyAccArgs A) {
 // ---- launchers ------------------------------------------------------------------
 static inline unsigned grid_for(size_t count) { return (unsigned)((count + FP_BLOCK - 1) / FP_BLOCK); }
 
-static void launch_decode(hipStream_t s, const void* params, const uint8_t* wire, int L, size_t count, SoA2 out) {
+static void launch_decode(hipStream_t s, const void* params, const uint8_t* wire, int L, size_t count, SoA2 out,
+                          const uint32_t* fx, const uint32_t* fy) {
   if (!count) return;
   hipLaunchKernelGGL((k_decode<NL_, false>), dim3(grid_for(count)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
-                     wire, L, count, out);
+                     wire, L, count, out, fx, fy);
 }
 
 static void launch_decode_plain(hipStream_t s, const void* params, const uint8_t* wire, int L, size_t count, SoA2 out) {
   if (!count) return;
   hipLaunchKernelGGL((k_decode<NL_, true>), dim3(grid_for(count)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
-                     wire, L, count, out);
+                     wire, L, count, out, nullptr, nullptr);
 }
 
 static void launch_validate(hipStream_t s, const void* params, const uint8_t* wire, int L, size_t count, int level,
@@ -821,15 +832,15 @@ static void launch_pairing(hipStream_t s, const void* params, const PairingConst
   if (!count) return;
   if (run < 1 || !ws) run = 1;
   const size_t lanes = (count + run - 1) / run;
-  // variant bit 1 (value 2) with a key table: the table is normalised (fixed_normalize_lane)
+  // variant bit 1 (value 2) with a key table: the table is normalised (fixed_normalize_lane); bit 2 (value 4): curve_a3
   if (fixed_tab && (mode == 1 || mode >= 3))
     hipLaunchKernelGGL((k_pairing<NL_, 1>), dim3(grid_for(lanes)), dim3(FP_BLOCK), 0, s,
                        (const FpParams<NL_>*)params, consts, a, b, out, count, mode, d1, d2, run, ws, sw, fixed_tab,
-                       mode == 1 ? (size_t)1 : tab_stride, (mode == 1 && (variant & 2)) ? 1 : 0);
+                       mode == 1 ? (size_t)1 : tab_stride, (mode == 1 && (variant & 2)) ? 1 : 0, 0);
   else
     hipLaunchKernelGGL((k_pairing<NL_, 0>), dim3(grid_for(lanes)), dim3(FP_BLOCK), 0, s,
                        (const FpParams<NL_>*)params, consts, a, b, out, count, mode, d1, d2, run, ws, sw, nullptr,
-                       (size_t)0, 0);
+                       (size_t)0, 0, (variant & 4) ? 1 : 0);
 }
 
 template <int NL>

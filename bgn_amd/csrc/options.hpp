@@ -40,6 +40,8 @@ struct Options {
   V decrypt_order_table{1};// lift over the secret order q2 (0: over n on the table of P); read by bgn_ctx_set_secret
   V fixed_normalize{1};    // per-key line tables divided by their c; read at context creation
   V miller_window{5};      // width of the NAF of n in the general Miller loop (3..5; 0: plain NAF); context creation
+  V miller_a3{1};          // Mult's lane kernel runs its Miller loop on the isomorphic curve y^2 = x^3 - 3x where the key has a
+                           // fourth root of -3 (p = 1 mod 3; 0: on y^2 = x^3 + x).  Reads back 0 for a key without one.
   V bsgs_max_log2{0};      // cap of the baby-step table, log2 entries (0: the default of bgn_ctx_setup_decryption)
   V fixed_window_bits{0};  // window width of P's table (8 or 16; 0: default)
   V fixed_window_bits_q{0};// window width of Q's table (8..22; 0: default)
@@ -107,6 +109,7 @@ inline const OptionDesc* option_table(size_t* n) {
       {"decrypt_order_table", &Options::decrypt_order_table, true, nullptr},
       {"fixed_normalize", &Options::fixed_normalize, true, nullptr},
       {"miller_window", &Options::miller_window, true, nullptr},
+      {"miller_a3", &Options::miller_a3, true, nullptr},
       {"bsgs_max_log2", &Options::bsgs_max_log2, true, nullptr},
       {"fixed_window_bits", &Options::fixed_window_bits, true, nullptr},
       {"fixed_window_bits_q", &Options::fixed_window_bits_q, true, nullptr},

@@ -14,7 +14,14 @@
 //     the host; a "-1" digit adds -A and multiplies by the line through V, -A;
 //   * the last addition step (V = -+A, vertical line) is skipped, as PBC does;
 //   * final exponent split as f^(p-1) = conj(f)/f, then ^l  ((p+1)/n = l);
-//   * sums of two products share one Montgomery reduction (round 5, see miller_double).
+//   * sums of two products share one Montgomery reduction (round 5, see miller_double);
+//   * Mult on the lane kernel runs the loop on the isomorphic curve y^2 = x^3 - 3x where p = 1 mod 3 (option
+//     miller_a3): for u in F_p with u^4 = -3, psi(x, y) = (u^2 x, u^3 y) maps y^2 = x^3 + x onto it and commutes
+//     with phi (u lies in F_p); f_{n,psi A} o psi is an F_p^*-multiple of f_{n,A}, so e'(psi A, psi B) = e(A, B)
+//     byte for byte.  There M = 3X^2 - 3Z^4 = 3(X - ZZ)(X + ZZ) is ONE product where a = 1 needs a sum of two.
+//     The formulas never use the curve's constant term, so the computation on the image is the image of the
+//     computation, step by step, for operands off the curve too (same exceptional cases, same zero norms).  psi
+//     costs nothing: k_decode multiplies by u^2 R^2 and u^3 R^2 instead of R^2 (engine.cpp, hostbig.hpp).
 //
 // The steps are written as explicit programs over storage slots (see
 // fpmont.hpp): long-lived state in six AGPR slots, four LDS slots (S0 is the
@@ -37,6 +44,7 @@ struct PairOperands {
   const u32* by;
   size_t sb;      // limb stride of B's arrays (1 with eb = 0 broadcasts one point)
   size_t eb;
+  int a3 = 0;     // wave-uniform: A and B are the images psi(A), psi(B) on y^2 = x^3 - 3x (see miller_double)
 };
 
 // Running state of the Miller loop, in AGPR slots.
@@ -56,7 +64,9 @@ struct Miller {
 // instead of 18 + 18, 12 carry passes instead of 24; per addition step 17 + 14 instead of 17 + 17.
 
 // f <- f^2 * l_{V,V}(phi(B)),  V <- 2V
-template <int NL>
+// A3: 1 / 0 = the curve coefficient a = -3 / a = 1 fixed at compile time (the loops of k_pairing: a run-time switch inside
+// the step cost both routes 1.5 %); -1 = by op.a3 at run time.
+template <int NL, int A3 = -1>
 __device__ __forceinline__ void miller_double(Miller<NL>& S, LFp<NL>* L, const PairOperands& op,
                                               const FpParams<NL>* __restrict__ P) {
   LFp<NL>* S0 = L;
@@ -68,9 +78,16 @@ __device__ __forceinline__ void miller_double(Miller<NL>& S, LFp<NL>* L, const P
   fp_sqrv(r, r, P, S0);                    // ZZ <2            (16)
   l_store(L1, r);                          // L1 = ZZ
   a_load(u, S.X);                          // <8
-  l_store(S0, u);                          // S0 = X
-  fp_lin1<3, 0>(u, u, P);                  // 3X <24
-  fp_mul2(w, S0, u, L1, r, P);             // M = X*3X + ZZ*ZZ <2   (8*24 + 2*2 = 196; curve a = 1)
+  if (A3 < 0 ? op.a3 != 0 : A3 != 0) {     // wave-uniform: curve a = -3, M = 3X^2 - 3ZZ^2 is ONE product
+    fp_lin2<1, -1, 2>(w, u, r, P);         // X - ZZ + 2p <10
+    l_store(S0, w);                        // S0 = X - ZZ
+    fp_lin2<3, 3, 0>(u, u, r, P);          // 3X + 3ZZ <30
+    fp_mul(w, S0, u, P);                   // M = (X - ZZ)*3(X + ZZ) <2   (10*30 = 300)
+  } else {
+    l_store(S0, u);                        // S0 = X
+    fp_lin1<3, 0>(u, u, P);                // 3X <24
+    fp_mul2(w, S0, u, L1, r, P);           // M = X*3X + ZZ*ZZ <2   (8*24 + 2*2 = 196; curve a = 1)
+  }
   a_store(S.T, w);                         // T = M
   a_load(r, S.Y);                          // <2
   a_load(u, S.Z);                          // <4
@@ -304,7 +321,7 @@ __device__ __forceinline__ void final_exp_with_inverse(Fp<NL>& g0, Fp<NL>& g1, M
 }
 
 // Miller loop for one pairing: leaves f in S.F0 / S.F1.
-template <int NL>
+template <int NL, int A3 = -1>
 __device__ __forceinline__ void miller_loop(Miller<NL>& S, LFp<NL>* L, const PairOperands& op,
                                             const PairingConsts* __restrict__ C,
                                             const FpParams<NL>* __restrict__ P) {
@@ -323,7 +340,7 @@ __device__ __forceinline__ void miller_loop(Miller<NL>& S, LFp<NL>* L, const Pai
   }
 #pragma unroll 1
   for (int i = C->naf_len - 2; i >= 0; --i) {
-    miller_double<NL>(S, L, op, P);
+    miller_double<NL, A3>(S, L, op, P);
     const int d = C->naf[i];
     if (d != 0 && i != 0) miller_add<NL>(S, L, op, d, P);
   }
@@ -416,7 +433,7 @@ __device__ __forceinline__ void win_make_affine(const WinTab& W, int k, const u3
 }
 
 // Miller loop over the width-w digits C->wnaf; leaves f in S.F0 / S.F1.
-template <int NL>
+template <int NL, int A3 = -1>
 __device__ __forceinline__ void miller_loop_w(Miller<NL>& S, LFp<NL>* L, const PairOperands& op, const WinTab& W,
                                               const PairingConsts* __restrict__ C,
                                               const FpParams<NL>* __restrict__ P) {
@@ -438,7 +455,7 @@ __device__ __forceinline__ void miller_loop_w(Miller<NL>& S, LFp<NL>* L, const P
     fp_zero(r);
     a_store(S.F1, r);
   }
-  miller_double<NL>(S, L, op, P);                          // V = 2A (Z <4), f = f_2
+  miller_double<NL, A3>(S, L, op, P);                          // V = 2A (Z <4), f = f_2
   PairOperands op2 = op;                                   // addend 2A
   if (maxd > 3) {
     win_store_f<NL>(S, W, 2, S0, P);
@@ -528,7 +545,7 @@ __device__ __forceinline__ void miller_loop_w(Miller<NL>& S, LFp<NL>* L, const P
   }
 #pragma unroll 1
   for (int i = C->wnaf_len - 2; i >= 0; --i) {
-    miller_double<NL>(S, L, op, P);
+    miller_double<NL, A3>(S, L, op, P);
     const int d = C->wnaf[i];
     if (d == 0) continue;
     const int ad = d < 0 ? -d : d;

@@ -126,6 +126,7 @@ def miller_schedule(n: int, window: int = 5):
 # with one reduction): a reduction is what every product, squaring or sum ends with (NL^2 multiply-adds), a sum of
 # two products carries a second multiplication (NL^2 more) under the same reduction.
 STEP_DBL = (15, 3, 4)       # ZZ, YY, M^2 squared; M, Y3, F0, F1 sums; Y*Z, Z3*ZZ, cim, ZZ*xB, M*t, Sn, g0, F0*F1 plain
+STEP_DBL_A3 = (15, 3, 3)    # on y^2 = x^3 - 3x (option miller_a3, keys with p = 1 mod 3): M = (X - ZZ)*3(X + ZZ) is a plain product
 STEP_ADD = (14, 3, 4)       # ZZ, HH, rr^2 squared; Y3, cre, F0, F1 sums
 STEP_MULF = (2, 0, 2)       # f * f_d: two sums
 TABLE_DBL = (5, 0, 2)       # walk over a normalised line table: a*xC, g0, F0*F1 plain; F0, F1 sums
@@ -197,7 +198,8 @@ def algorithmic_mads_per_pairing(fx, run: int = 16, window: int = 5, segments: i
 def pairing_counts(fx, run: int = 16, window: int = 5):
     """(reductions, squarings, sums of two products) of one pairing of k_pairing<NL, 0>: the windowed Miller loop of
     pairing.hpp with round 5's step programs (STEP_*), norms (both passes), the shared inversion's peel,
-    conj(f)^2 / N, ^l and the conversions out of Montgomery form."""
+    conj(f)^2 / N, ^l and the conversions out of Montgomery form.  A key whose p is 1 mod 3 runs the loop on the
+    a = -3 curve (the default of option miller_a3): every doubling step has one sum of two products fewer."""
     n, l = int(fx["n"], 16), int(fx["l"])
     dbl, add, threes, pre = miller_schedule(n, window)
     lb = l.bit_length()
@@ -211,6 +213,8 @@ def pairing_counts(fx, run: int = 16, window: int = 5):
     if window >= 3:
         squares += STEP_DBL[1] + npts * STEP_ADD[1] + (npts + 1)
         sops += STEP_DBL[2] + npts * STEP_ADD[2] + (npts - 1) * STEP_MULF[2]
+    if int(fx["p"], 16) % 3 == 1:
+        sops -= (dbl + (1 if window >= 3 else 0)) * (STEP_DBL[2] - STEP_DBL_A3[2])
     return red + INVERSION_PRODUCTS / run, float(squares), float(sops)
 
 

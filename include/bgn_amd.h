@@ -132,7 +132,10 @@ int bgn_ctx_set_memory_budget(bgn_ctx* c, uint64_t bytes);
  * fixed_window_bits* and fixed_signed_q on first Encrypt — must be in place before that step; a value that arrives after its table is
  * built is refused with BGN_E_STATE, never accepted silently: miller_window and fixed_normalize always — they are
  * creation-time options, set BGN_MILLER_WINDOW / BGN_FIXED_NORMALIZE in the environment —, fixed_window_bits* and fixed_signed_q once the
- * window tables exist).  bgn_ctx_reset_options goes back to the values the context was created with and re-applies
+ * window tables exist).  miller_a3 (default 1; 0: off): Mult's lane kernel runs its Miller loop on the isomorphic curve
+ * y^2 = x^3 - 3x — same bytes, one product fewer per doubling step; bgn_ctx_get_option reads back 1 only where the
+ * route is active, i.e. the option is on AND p = 1 mod 3 (F_p then holds a fourth root of -3).
+ * bgn_ctx_reset_options goes back to the values the context was created with and re-applies
  * those with a side effect (memory_budget_mb: the budget in force is the restored one).  bgn_option_name(i)
  * enumerates the names (null past the end).  Unknown name: BGN_E_ARG.  There is no counterpart in the reference (PBC has no tunables on this path); the
  * nearest is the package-level state of gsbs.go:12-15. */
