@@ -28,6 +28,11 @@
 #include "dispatch.hpp"      // (and options.hpp)
 #include "combiner.hpp"
 
+namespace {
+int ensure_arena(bgn_ctx* c, size_t bytes);      // (carve.hpp grows the workspace through it)
+}
+#include "carve.hpp"
+
 using namespace bgn;
 
 namespace {
@@ -51,6 +56,14 @@ int fail(int code, const char* fmt, ...) {
   } while (0)
 
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the elements of v from `off` on
+SoA2 view(SoA2 v, size_t off) {
+  v.c0 += off;
+  v.c1 += off;
+  if (v.inf) v.inf += off;
+  return v;
+}
 
 }  // namespace
 
@@ -132,7 +145,7 @@ struct bgn_ctx {
   // NAF is that of q2 = n / q1 — half the Miller steps of e(P, .)
   PairingConsts* d_consts_sk = nullptr;
   uint32_t* d_fixedpair_sk = nullptr;
-  bool fixed_normalized = false;       // the key tables hold a/c, b/c (fixedpair.hpp): pairing variant 2
+  bool fixed_normalized = false;       // the key tables hold a/c, b/c (fixedpair.hpp): PairingJob::tab_normalized
   BsgsParams bsgs{};
   bool have_tables = false;
 
@@ -374,26 +387,6 @@ struct StreamOrder {
       c->busy_stream = s;
       c->busy_valid = true;
     }
-  }
-};
-
-// Carves SoA2 views out of the arena.
-struct Carver {
-  uint8_t* base;
-  size_t off = 0;
-  explicit Carver(uint8_t* b) : base(b) {}
-  void* take(size_t bytes) {
-    void* p = base ? base + off : nullptr;
-    off += round_up(bytes, 256);
-    return p;
-  }
-  SoA2 soa(int nl, size_t stride, bool with_inf) {
-    SoA2 s;
-    s.c0 = (uint32_t*)take((size_t)nl * stride * 4);
-    s.c1 = (uint32_t*)take((size_t)nl * stride * 4);
-    s.inf = with_inf ? (uint8_t*)take(stride) : nullptr;
-    s.stride = stride;
-    return s;
   }
 };
 
@@ -883,8 +876,10 @@ int bgn_ctx_setup_decryption(bgn_ctx* c, uint64_t msg_space) {
   // g = e(P,P)^sk  (bgn.go:198-199)
   // (over P's line table: the batch kernel k_pairing<., 0> is then launched by Mult alone, which keeps its
   // rocprofv3 average the per-batch figure bench.py reports)
-  kt->pairing(nullptr, c->d_params, c->d_consts, c->key_P(), c->key_P(), t1, 1, 1, 0, 0, 1, nullptr, 0, c->d_fixedpair, 1,
-              c->fixed_normalized ? 2 : 0);
+  PairingJob pp;
+  pp.consts = c->d_consts; pp.a = pp.b = c->key_P(); pp.out = t1; pp.count = 1;
+  pp.shape = PairShape::Broadcast; pp.tab = c->d_fixedpair; pp.tab_normalized = c->fixed_normalized;
+  kt->pairing(nullptr, c->d_params, pp);
   kt->to_mont(nullptr, c->d_params, t1.c0, t1.c1, 1, 1);
   gt_pow_launch(c, nullptr, t1, c->d_sk, 0, c->sk_len, g, 1);
   kt->to_mont(nullptr, c->d_params, g.c0, g.c1, 1, 1);
@@ -968,6 +963,26 @@ static size_t pairing_ws_bytes(const bgn_ctx* c, Family f, size_t sw, int lane_s
   return b > lane ? b : lane;
 }
 
+// The job on the lane groups (family Quad) or the cooperative kernel (family Coop; coop_one_launch: without the
+// workspace, i.e. one launch with the Fermat inversion on the waves).  Returns the kernel's name, or null when nothing
+// was launched — the family is Lane, or the launcher declined — and the caller goes on to the lane kernel.
+static const char* launch_group_pairing(bgn_ctx* c, hipStream_t s, Family f, const PairingJob& job, bool coop_one_launch = false) {
+  if (f == Family::Quad && quad_pairing_launch(c->nl, s, c->d_params, c->p_bits + 1, job)) return quad_pairing_kernel_name(c->nl);
+  if (f == Family::Coop) {
+    PairingJob j = job;
+    if (coop_one_launch) j.ws = nullptr;
+    if (coop_pairing_launch(c->nl, s, c->d_params, c->p_bits + 1, j)) return coop_pairing_kernel_name(c->nl);
+  }
+  return nullptr;
+}
+
+// The job on the lane kernel, which serves every shape and limb count.  Returns the kernel's name.
+static const char* launch_lane_pairing(bgn_ctx* c, hipStream_t s, PairingJob job) {
+  job.run = pairing_run(c, job.count);
+  c->kt->pairing(s, c->d_params, job);
+  return job.shape == PairShape::Each || job.shape == PairShape::Poly ? c->kt->pairing_kernel_name : c->kt->pairing_table_kernel_name;
+}
+
 // The lane-group pairing's Miller loop over the width-w NAF (quad.hpp k_pairing_quad_wtab: per-pairing table of the odd
 // multiples of A and their Miller values, 9 KB per pairing at 1024 bits): 9 % fewer rounds, two more table launches
 // and two more inversion launches.  Returns the width (0: the plain NAF).  Option quad_window: 0 never, 1 always.
@@ -979,9 +994,10 @@ static int quad_window(const bgn_ctx* c, size_t count) {
   return w;
 }
 
-static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, const uint8_t* b, size_t nb, int mode,
-                         size_t d1, size_t d2, uint8_t* out, hipStream_t s, const uint8_t* r_be, size_t r_len,
-                         bool first_piece, bool last_piece) {
+// Mult (shape Each) or makeL2 (shape Broadcast: b == null, the second operand is the key's P)
+static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, const uint8_t* b, size_t nb, PairShape shape,
+                         uint8_t* out, hipStream_t s, const uint8_t* r_be, size_t r_len, bool first_piece, bool last_piece) {
+  const bool l2 = shape == PairShape::Broadcast;
   std::lock_guard<std::mutex> lk(c->mu);
   StreamOrder order(c, s);
   HIP_TRY(hipSetDevice(c->device));
@@ -991,36 +1007,24 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
   }
   const KernelTable* kt = c->kt;
   const size_t sa = round_up(na, 64), sb = round_up(nb ? nb : 1, 64), so = round_up(count, 64);
-  Carver probe(nullptr);
-  probe.soa(c->nl, sa, true);
-  if (nb) probe.soa(c->nl, sb, true);
-  probe.soa(c->nl, so, false);
   const DispatchView dv = dispatch_view(c);
-  const Family fam = family(dv, (Work)mode, count);
+  const Family fam = family(dv, l2 ? Work::MakeL2 : Work::Mult, count);
   // makeL2 on the lane groups (a mid-size batch) walks the key's normalised line table
-  const bool quad_tab = fam == Family::Quad && mode == 1;
+  const bool quad_tab = fam == Family::Quad && l2;
   const int qwin = (fam == Family::Quad && !quad_tab) ? quad_window(c, count) : 0;
-  const size_t ws_bytes = pairing_ws_bytes(c, fam, so, mode == 1 ? 3 : c->pair_ws_slots, qwin);
-  probe.take(ws_bytes);
-  if (r_be) {
-    probe.soa(c->nl, so, false);
-    probe.soa(c->nl, so, false);
-  }
-  int rc = ensure_arena(c, probe.off);
-  if (rc) return rc;
-  Carver cv(c->arena);
-  SoA2 A = cv.soa(c->nl, sa, true);
-  SoA2 B = nb ? cv.soa(c->nl, sb, true) : c->key_P();
-  SoA2 O = cv.soa(c->nl, so, false);
-  uint32_t* ws = (uint32_t*)cv.take(ws_bytes);   // lane kernel: room for the windowed loop's (dA, f_d)
-  SoA2 T1{}, T2{};
-  if (r_be) {
-    T1 = cv.soa(c->nl, so, false);
-    T2 = cv.soa(c->nl, so, false);
-  }
+  const size_t ws_bytes = pairing_ws_bytes(c, fam, so, l2 ? 3 : c->pair_ws_slots, qwin);
+  SoA2 A{}, B = c->key_P(), O{}, T1{}, T2{};
+  uint32_t* ws = nullptr;
+  if (int rc = carve(c, [&](Ws& w) {
+    A = w.g1(sa);
+    if (nb) B = w.g1(sb);
+    O = w.gt(so);
+    ws = (uint32_t*)w.cv.take(ws_bytes);   // lane kernel: room for the windowed loop's (dA, f_d)
+    if (r_be) { T1 = w.gt(so); T2 = w.gt(so); }
+  })) return rc;
   // Mult on the lane kernel runs on the a = -3 curve where the key admits it: A and B are then decoded through the
-  // isomorphism (u^2 R^2, u^3 R^2 in place of R^2).  Every other mode and kernel family works on a = 1.
-  const bool a3_ok = mode == 0 && nb && c->d_a3 && opt(c, &Options::miller_a3) != 0;
+  // isomorphism (u^2 R^2, u^3 R^2 in place of R^2).  Every other shape and kernel family works on a = 1.
+  const bool a3_ok = shape == PairShape::Each && nb && c->d_a3 && opt(c, &Options::miller_a3) != 0;
   bool a3 = a3_ok && fam == Family::Lane;
   auto decode_operands = [&] {
     kt->decode(s, c->d_params, a, c->L, na, A, a3 ? c->d_a3 : nullptr, a3 ? c->d_a3 + c->nl : nullptr);
@@ -1028,26 +1032,22 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
   };
   decode_operands();
   if (first_piece) HIP_TRY(hipEventRecord(c->ev0, s));
-  const char* kname = "";
-  // coop_fermat=1: the one-launch form with the Fermat inversion on the waves (A/B measurements)
-  const bool cf = opt(c, &Options::coop_fermat) == 1;
+  PairingJob job;
+  job.consts = c->d_consts; job.a = A; job.b = B; job.out = O;
+  job.count = count; job.shape = shape;
+  job.ws = ws; job.sw = so; job.window = qwin;
   // makeL2 on the waves walks the key's normalised line table (6 / 4 products per step in 2 / 3 rounds instead of
   // a full pairing's 18 / 36 in 3 / 6); BGN_COOP_TABLE=0 keeps the general program
-  const uint32_t* ctab = (mode == 1 && dv.table_walk) ? c->d_fixedpair : nullptr;
-  if (fam == Family::Quad && quad_pairing_launch(c->nl, s, c->d_params, c->d_consts, A, B, O, count, mode, 0, 0, ws, so, c->p_bits + 1,
-                                  quad_tab ? c->d_fixedpair : nullptr, qwin)) {
-    kname = quad_pairing_kernel_name(c->nl);
-  } else if (fam == Family::Coop && coop_pairing_launch(c->nl, s, c->d_params, c->d_consts, A, B, O, count, mode, 0, 0,
-                                                        cf ? nullptr : ws, so, c->p_bits + 1, ctab)) {
-    kname = coop_pairing_kernel_name(c->nl);
-  } else {
+  if (quad_tab || (fam == Family::Coop && l2 && dv.table_walk)) job.tab = c->d_fixedpair;
+  // coop_fermat=1: the one-launch form with the Fermat inversion on the waves (A/B measurements)
+  const char* kname = launch_group_pairing(c, s, fam, job, opt(c, &Options::coop_fermat) == 1);
+  if (!kname) {
     if (a3_ok && !a3) {          // a lane-group or cooperative launcher refused: the lane kernel takes its own route
       a3 = true;
       decode_operands();
     }
-    kt->pairing(s, c->d_params, c->d_consts, A, B, O, count, mode, d1, d2, pairing_run(c, count), ws, so,
-                (mode == 1) ? c->d_fixedpair : nullptr, 1, (mode == 1) ? (c->fixed_normalized ? 2 : 0) : (a3 ? 4 : 0));
-    kname = mode == 1 ? kt->pairing_table_kernel_name : kt->pairing_kernel_name;
+    job.tab = l2 ? c->d_fixedpair : nullptr; job.tab_normalized = c->fixed_normalized; job.curve_a3 = a3;
+    kname = launch_lane_pairing(c, s, job);
   }
   if (first_piece) c->last_kernel = kname;
   if (last_piece) {
@@ -1062,17 +1062,17 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
 
 // Mult / makeL2 over `count` pairs, in pieces of at most 2^22: the workspace of a piece (7.4 KB per pairing with
 // the width-5 loop) stays at 31 GB however long the arrays are.
-static int pairing_common(bgn_ctx* c, size_t count, const uint8_t* a, const uint8_t* b, int mode, size_t d1, size_t d2,
-                          uint8_t* out, hipStream_t s, const uint8_t* r_be = nullptr, size_t r_len = 0) {
+static int pairing_common(bgn_ctx* c, size_t count, const uint8_t* a, const uint8_t* b, PairShape shape, uint8_t* out,
+                          hipStream_t s, const uint8_t* r_be = nullptr, size_t r_len = 0) {
   if (!count) return BGN_OK;
   if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
   const size_t piece = (size_t)1 << 22, eb = (size_t)2 * c->L;
   for (size_t off = 0; off < count;) {
     size_t n = count - off < piece ? count - off : piece;
-    n = rounds_head(dispatch_view(c), (Work)mode, n);      // whole rounds of the lane kernel first (dispatch.hpp)
+    n = rounds_head(dispatch_view(c), b ? Work::Mult : Work::MakeL2, n);      // whole rounds of the lane kernel first (dispatch.hpp)
     // the measurement hooks span the whole call: first event on the head piece, second on the last one; the kernel
     // reported is the head piece's (it does nearly all the work of a batch cut into rounds + remainder)
-    int rc = pairing_chunk(c, n, a + off * eb, n, b ? b + off * eb : nullptr, b ? n : 0, mode, d1, d2, out + off * eb, s,
+    int rc = pairing_chunk(c, n, a + off * eb, n, b ? b + off * eb : nullptr, b ? n : 0, shape, out + off * eb, s,
                            r_be ? r_be + off * r_len : nullptr, r_len, off == 0, off + n >= count);
     if (rc) return rc;
     off += n;
@@ -1084,12 +1084,12 @@ int bgn_mult_batch_dev(bgn_ctx* c, size_t count, const uint8_t* a, const uint8_t
                        uint8_t* out, void* stream) {
   if (!c || (count && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
   if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
-  return pairing_common(c, count, a, b, 0, 0, 0, out, (hipStream_t)stream, r_be, r_len);
+  return pairing_common(c, count, a, b, PairShape::Each, out, (hipStream_t)stream, r_be, r_len);
 }
 
 int bgn_make_l2_batch_dev(bgn_ctx* c, size_t count, const uint8_t* a, uint8_t* out, void* stream) {
   if (!c || (count && (!a || !out))) return fail(BGN_E_ARG, "null argument");
-  return pairing_common(c, count, a, nullptr, 1, 0, 0, out, (hipStream_t)stream);
+  return pairing_common(c, count, a, nullptr, PairShape::Broadcast, out, (hipStream_t)stream);
 }
 
 // ---- Add / Sub / Neg / MultConst / Encrypt ------------------------------------------------
@@ -1104,15 +1104,6 @@ int run_for(size_t count) {
   if (r < 1) r = 1;
   return (int)r;
 }
-
-struct Ws {   // workspace planner: two passes (size, then carve)
-  bgn_ctx* c;
-  Carver cv;
-  explicit Ws(bgn_ctx* c_, uint8_t* base) : c(c_), cv(base) {}
-  SoA2 g1(size_t stride) { return cv.soa(c->nl, stride, true); }
-  SoA2 gt(size_t stride) { return cv.soa(c->nl, stride, false); }
-  uint32_t* fp(size_t stride) { return (uint32_t*)cv.take((size_t)c->nl * stride * 4); }
-};
 
 // out (plain, with inf) = A (+/-) B on G1, both canonical Montgomery
 void g1_add_launch(bgn_ctx* c, hipStream_t s, SoA2 A, SoA2 B, SoA2 O, uint32_t* prefix, size_t count, bool negate_b,
@@ -1130,8 +1121,8 @@ void g1_add_launch(bgn_ctx* c, hipStream_t s, SoA2 A, SoA2 B, SoA2 O, uint32_t* 
   c->kt->g1_add(s, c->d_params, c->d_consts, a);
 }
 
-void g1_mul_launch(bgn_ctx* c, hipStream_t s, SoA2 B, const uint8_t* k, size_t kstride, size_t klen, SoA2 O,
-                   size_t count) {
+// O = k * B on the binary ladder, every element
+G1MulArgs g1_mul_args(SoA2 B, const uint8_t* k, size_t kstride, size_t klen, SoA2 O, size_t count) {
   G1MulArgs a;
   a.bx = B.c0; a.by = B.c1; a.binf = B.inf; a.sb = B.stride;
   a.bdiv = 0;
@@ -1140,6 +1131,12 @@ void g1_mul_launch(bgn_ctx* c, hipStream_t s, SoA2 B, const uint8_t* k, size_t k
   a.count = count;
   a.wtab = nullptr; a.winf = nullptr; a.wcap = 0; a.wbits = 4;
   a.only = nullptr; a.only_mask = 0;
+  return a;
+}
+
+void g1_mul_launch(bgn_ctx* c, hipStream_t s, SoA2 B, const uint8_t* k, size_t kstride, size_t klen, SoA2 O,
+                   size_t count) {
+  G1MulArgs a = g1_mul_args(B, k, kstride, klen, O, count);
   // per-element bases: fixed windows over a table of 1*B .. (2^w - 1)*B per element (ops.hpp).  Scalars of 128 bits and
   // more: w = 4, 12 KB of scratch each (measured at 2^16 elements against the binary ladder: 1.4x at 256 bits, 1.67x at
   // 1024 bits; option g1_mul_window = 0 keeps the binary ladder); shorter ones (plaintext-sized constants, the
@@ -1258,17 +1255,12 @@ int ensure_fixed_tables(bgn_ctx* c) {
   SoA2 base, pw;
   uint8_t* k1 = nullptr;
   uint32_t* prefix = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     base = w.g1(64);
     pw = w.g1(sp);
     prefix = w.fp(sr);
     k1 = (uint8_t*)w.cv.take(npt * klen);
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   std::vector<uint8_t> h1(npt * klen, 0);
   for (size_t b = 0, o = 0; b < 2; o += np[b], ++b)
     for (size_t i = 0; i < np[b]; ++i) h1[(o + i) * klen + (klen - 1 - i / 8)] = (uint8_t)(1u << (i % 8));   // 2^i
@@ -1286,15 +1278,7 @@ int ensure_fixed_tables(bgn_ctx* c) {
   // the entries 2^i * B of both tables by the ladder kernel, one launch per base (the base is a broadcast point)
   for (size_t b = 0, o = 0; b < 2; o += np[b], ++b) {
     const SoA2 key = b ? c->key_Q() : c->key_P();
-    G1MulArgs a;
-    a.bx = key.c0; a.by = key.c1; a.binf = nullptr; a.sb = 1;
-    a.bdiv = 0;
-    a.k = k1 + o * klen; a.kstride = klen; a.klen = klen;
-    a.ox = pw.c0 + o; a.oy = pw.c1 + o; a.oinf = pw.inf + o; a.so = pw.stride;
-    a.count = np[b];
-    a.wtab = nullptr; a.winf = nullptr; a.wcap = 0; a.wbits = 4;
-    a.only = nullptr; a.only_mask = 0;
-    kt->g1_mul(nullptr, c->d_params, c->d_consts, a);
+    kt->g1_mul(nullptr, c->d_params, c->d_consts, g1_mul_args(key, k1 + o * klen, klen, klen, view(pw, o), np[b]));
   }
   kt->to_mont(nullptr, c->d_params, pw.c0, pw.c1, pw.stride, npt);
   for (size_t b = 0, o = 0; b < 2; o += np[b], ++b) {
@@ -1545,7 +1529,9 @@ int ensure_gt_table(bgn_ctx* c) {
   const SoA2 g = c->key_eQQ();
   // e(Q,Q) (bgn.go:306,469): one pairing per key, here rather than at context creation so that keys used
   // in deterministic mode never pay for it
-  kt->pairing(nullptr, c->d_params, c->d_consts, c->key_Q(), c->key_Q(), g, 1, 0, 0, 0, 1, nullptr, 0, nullptr, 0, 0);
+  PairingJob qq;
+  qq.consts = c->d_consts; qq.a = qq.b = c->key_Q(); qq.out = g; qq.count = 1;
+  kt->pairing(nullptr, c->d_params, qq);
   kt->to_mont(nullptr, c->d_params, g.c0, g.c1, 1, 1);
   kt->gt_tab_pows(nullptr, c->d_params, g.c0, g.c1, wbits, W, tab);
   for (int k = 1; k < wbits; ++k) {
@@ -1601,14 +1587,9 @@ int addsub_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint
     // of the lanes' runs (one F_p per element)
     const size_t st1 = round_up(count, 64);
     uint32_t* pfx = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {
-      Ws w(c, pass ? c->arena : nullptr);
+    if (int rc = carve(c, [&](Ws& w) {
       pfx = w.fp(st1);
-      if (!pass) {
-        int rc = ensure_arena(c, w.cv.off);
-        if (rc) return rc;
-      }
-    }
+    })) return rc;
     HIP_TRY(hipEventRecord(c->ev0, s));
     c->kt->g1_add_wire(s, c->d_params, c->d_consts, a, b, c->L, count, run_for(count), subtract ? 1 : 0, pfx, st1, out);
     HIP_TRY(hipEventRecord(c->ev1, s));
@@ -1630,8 +1611,7 @@ int addsub_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint
   const size_t st = round_up(count, 64);
   SoA2 A, B, O, T1, T2;
   uint32_t* prefix = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     if (level == 1) {
       A = w.g1(st); B = w.g1(st); O = w.g1(st); prefix = w.fp(st);
       if (r_be) { T1 = w.g1(st); T2 = w.g1(st); }
@@ -1639,11 +1619,7 @@ int addsub_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint
       A = w.gt(st); B = w.gt(st); O = w.gt(st);
       if (r_be) { T1 = w.gt(st); T2 = w.gt(st); }
     }
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   const KernelTable* kt = c->kt;
   if (level == 1) {
     // wire-to-wire G1 addition runs on plain residues: no Montgomery conversion of operands or sum (ops.hpp)
@@ -1705,14 +1681,9 @@ int bgn_neg_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, uin
   }
   const size_t st = round_up(count, 64);
   SoA2 A;
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     A = (level == 1) ? w.g1(st) : w.gt(st);
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   const KernelTable* kt = c->kt;
   // Neg(c) = Sub(encryptZero(), c), bgn.go:436-438.  Level 1: (x, y) -> (x, p - y); level 2: 1 / c = conj(c) on
   // GT (norm 1), (re, im) -> (re, p - im).  No field product at all: plain residues in, one coordinate negated.
@@ -1749,8 +1720,7 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
   SoA2 A, O, T1, T2;
   uint32_t* prefix = nullptr;
   uint32_t* qws = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     if (level == 1) {
       A = w.g1(st); O = w.g1(st);
       if (r_be) { T1 = w.g1(st); T2 = w.g1(st); prefix = w.fp(st); }
@@ -1759,19 +1729,9 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
       if (r_be) { T1 = w.gt(st); T2 = w.gt(st); }
     }
     if (qws_bytes) qws = (uint32_t*)w.cv.take(qws_bytes);
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   const KernelTable* kt = c->kt;
   kt->decode(s, c->d_params, a, c->L, count, A, nullptr, nullptr);
-  auto view = [](SoA2 v, size_t off) {
-    v.c0 += off;
-    v.c1 += off;
-    if (v.inf) v.inf += off;
-    return v;
-  };
   HIP_TRY(hipEventRecord(c->ev0, s));
   c->last_kernel = "";
   for (size_t off = 0; off < count;) {
@@ -1791,13 +1751,7 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
       uint8_t* flags = quad_g1_mul_launch(c->nl, s, c->d_params, Av, kv, k_len, k_len, Ov, n, qws, round_up(n, 64), c->p_bits + 1);
       if (flags) {
         // the elements whose ladder met an exceptional case of the formulas (flag bit 1): the exact lane kernel
-        G1MulArgs g;
-        g.bx = Av.c0; g.by = Av.c1; g.binf = Av.inf; g.sb = Av.stride;
-        g.bdiv = 0;
-        g.k = kv; g.kstride = k_len; g.klen = k_len;
-        g.ox = Ov.c0; g.oy = Ov.c1; g.oinf = Ov.inf; g.so = Ov.stride;
-        g.count = n;
-        g.wtab = nullptr; g.winf = nullptr; g.wcap = 0; g.wbits = 4;
+        G1MulArgs g = g1_mul_args(Av, kv, k_len, k_len, Ov, n);
         g.only = flags; g.only_mask = 2u;
         const int64_t hook = opt(c, &Options::test_mc_fallback);
         if (hook == 2) {                               // tests: how many elements did the lane groups flag?
@@ -1853,45 +1807,27 @@ int bgn_encrypt_batch_dev(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t 
   const size_t st = round_up(count, 64);
   SoA2 G, H, O;
   uint32_t* prefix = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     G = w.g1(st);
     if (r_be) { H = w.g1(st); O = w.g1(st); prefix = w.fp(st); }
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   const KernelTable* kt = c->kt;
-  {
-    int rc = ensure_fixed_tables(c);      // may re-carve the arena: G/H/O are re-derived below
-    if (rc) return rc;
-  }
+  if (int rc = ensure_fixed_tables(c)) return rc;      // may re-carve the arena: G/H/O are re-derived below
   if (fixed_fits(c, x_len) && (!r_be || fixed_fits(c, r_len, true))) {
-    for (int pass = 0; pass < 2; ++pass) {
-      Ws w(c, pass ? c->arena : nullptr);
+    if (int rc = carve(c, [&](Ws& w) {
       G = w.g1(st);
       prefix = w.fp(st);
-      if (!pass) {
-        int rc = ensure_arena(c, w.cv.off);
-        if (rc) return rc;
-      }
-    }
+    })) return rc;
     int rc = fixed_base_product(c, s, G, prefix, x_be, x_len, r_be, r_len, count, true);   // bgn.go:344-350 fused
     if (rc) return rc;
     kt->encode(s, G.inf, G.c0, G.c1, G.stride, c->L, count, out);
     HIP_TRY(hipGetLastError());
     return BGN_OK;
   }
-  for (int pass = 0; pass < 2; ++pass) {   // long scalars: generic ladders
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {   // long scalars: generic ladders
     G = w.g1(st);
     if (r_be) { H = w.g1(st); O = w.g1(st); prefix = w.fp(st); }
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   HIP_TRY(hipEventRecord(c->ev0, s));
   g1_mul_launch(c, s, c->key_P(), x_be, x_len, x_len, G, count);                // G.PowBig(pk.P, x), bgn.go:344
   if (r_be) {
@@ -2468,19 +2404,14 @@ static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct,
   uint32_t* pws = nullptr;
   const DispatchView dv = dispatch_view(c);
   const Family lift = family(dv, Work::Lift, count);
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     A = (level == 1) ? w.g1(st) : w.gt(st);
     X = w.gt(st);
     Y = w.gt(st);
     if (level == 1) pws = (uint32_t*)w.cv.take(pairing_ws_bytes(c, lift, st, 3));
     todo = (uint32_t*)w.cv.take(st * 4);
     todo_count = (uint32_t*)w.cv.take(256);
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   const KernelTable* kt = c->kt;
   kt->decode(s, c->d_params, ct, c->L, count, A, nullptr, nullptr);
   SoA2 base = A;
@@ -2489,25 +2420,22 @@ static int decrypt_piece(bgn_ctx* c, size_t count, int level, const uint8_t* ct,
     // lift is f_{q2,q1*P}(phi(C))^((p-1)*l), which the power by q1 below turns into the same e(C, P)^q1.
     const bool sk_tab = c->d_fixedpair_sk != nullptr;
     if (first_piece) HIP_TRY(hipEventRecord(c->ev2, s));
-    const char* aname = "";
+    PairingJob job;                                                  // the table walk, over q2 when its table exists
+    job.consts = sk_tab ? c->d_consts_sk : c->d_consts; job.a = A; job.b = c->key_P(); job.out = X;
+    job.count = count; job.shape = PairShape::Broadcast;
+    job.ws = pws; job.sw = st;
+    job.tab = sk_tab ? c->d_fixedpair_sk : c->d_fixedpair; job.tab_normalized = c->fixed_normalized;
     // a small batch lifts with the wave-cooperative kernel over the same line table (two or three rounds of products
     // per step instead of a whole table loop on a single lane: 28 ms at a 1024-bit key); the power by q1 below
     // gives the same e(C, P)^q1 whichever scalar the loop ran over
-    const bool ctab = dv.table_walk;                                 // the table walk, over q2 when its table exists
     // ... and a mid-size batch with the lane-group kernel (sixteen lanes per lift, two or three rounds per step)
-    if (lift == Family::Quad &&
-        quad_pairing_launch(c->nl, s, c->d_params, sk_tab ? c->d_consts_sk : c->d_consts, A, c->key_P(), X, count, 1, 0, 0, pws,
-                            st, c->p_bits + 1, sk_tab ? c->d_fixedpair_sk : c->d_fixedpair)) {
-      aname = quad_pairing_kernel_name(c->nl);
-    } else if (lift == Family::Coop &&
-        coop_pairing_launch(c->nl, s, c->d_params, (ctab && sk_tab) ? c->d_consts_sk : c->d_consts, A, c->key_P(), X, count, 1,
-                            0, 0, pws, st, c->p_bits + 1, ctab ? (sk_tab ? c->d_fixedpair_sk : c->d_fixedpair) : nullptr)) {
-      aname = coop_pairing_kernel_name(c->nl);
-    } else {
-      kt->pairing(s, c->d_params, sk_tab ? c->d_consts_sk : c->d_consts, A, c->key_P(), X, count, 1, 0, 0,
-                  pairing_run(c, count), pws, st, sk_tab ? c->d_fixedpair_sk : c->d_fixedpair, 1, c->fixed_normalized ? 2 : 0);
-      aname = kt->pairing_table_kernel_name;
+    PairingJob group = job;
+    if (lift == Family::Coop && !dv.table_walk) {                    // the waves' general program, as Mult runs it
+      group.consts = c->d_consts;
+      group.tab = nullptr;
     }
+    const char* aname = launch_group_pairing(c, s, lift, group);
+    if (!aname) aname = launch_lane_pairing(c, s, job);
     if (first_piece) c->aux_kernel = aname;
     if (last_piece) {
       HIP_TRY(hipEventRecord(c->ev3, s));
@@ -2683,8 +2611,7 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
   const int qwin_main = fam == Family::Quad ? quad_window(c, np) : 0, qwin_tail = tail_fam == Family::Quad ? quad_window(c, tail_pairs) : 0;
   SoA2 E, Tt, Vt;
   uint32_t* pws = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     E = w.gt(sp);
     if (multi) {
       Tt = w.g1(d1 * Qp);
@@ -2693,11 +2620,7 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
     size_t ws_b = pairing_ws_bytes(c, fam, sp, chunk ? 3 : c->pair_ws_slots, qwin_main);
     if (tail_direct) ws_b = std::max(ws_b, pairing_ws_bytes(c, tail_fam, tail_sp, c->pair_ws_slots, qwin_tail));
     pws = (uint32_t*)w.cv.take(ws_b);
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   uint32_t* tab = nullptr;
   const size_t ts = multi ? d1 * Qp : round_up(cp * dt, 64);
   if (chunk) {
@@ -2710,12 +2633,6 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
     tab = c->poly_tab;
   }
   const KernelTable* kt = c->kt;
-  auto view = [](SoA2 v, size_t off) {
-    v.c0 += off;
-    v.c1 += off;
-    if (v.inf) v.inf += off;
-    return v;
-  };
   int tables_used = 0;
   for (size_t q0 = 0, nq = 0; q0 < npoly; q0 += nq) {
     nq = (npoly - q0 < cp) ? npoly - q0 : cp;
@@ -2743,22 +2660,22 @@ int poly_mult_core(bgn_ctx* c, hipStream_t s, size_t npoly, size_t d1, size_t d2
       kt->poly_acc(s, c->d_params, pa);
       continue;
     }
+    PairingJob job;                                                                // pk.Mult(coeff1, coeff2), poly.go:146
+    job.consts = c->d_consts; job.a = Aq; job.b = Bq; job.out = E;
+    job.count = pairs; job.shape = PairShape::Poly; job.d1 = d1; job.d2 = d2;
+    job.ws = pws; job.sw = sw;
     if (!direct) {
       const SoA2 T = tab_on_a ? Aq : Bq, V = tab_on_a ? Bq : Aq;
       kt->fixedpair_build_batch(s, c->d_params, c->d_consts, T, nq * dt, tab, ts);
-      kt->pairing(s, c->d_params, c->d_consts, V, T, E, pairs, tab_on_a ? 3 : 4, d1, d2, pairing_run(c, pairs), pws, sp,
-                  tab, ts, 0);                                                     // pk.Mult(coeff1, coeff2), poly.go:146
+      job.a = V; job.b = T; job.shape = tab_on_a ? PairShape::PolyTabA : PairShape::PolyTabB;
+      job.tab = tab; job.tab_stride = ts;
+      launch_lane_pairing(c, s, job);
       if (!tables_used) tables_used = 1;
-    } else if (q_fam == Family::Quad && quad_pairing_launch(c->nl, s, c->d_params, c->d_consts, Aq, Bq, E, pairs, 2, d1, d2, pws, sw,
-                                             c->p_bits + 1, nullptr, tail ? qwin_tail : qwin_main)) {
-      c->last_kernel = quad_pairing_kernel_name(c->nl);
-    } else if (q_fam == Family::Coop && coop_pairing_launch(c->nl, s, c->d_params, c->d_consts, Aq, Bq, E, pairs, 2, d1, d2, pws, sw,
-                                             c->p_bits + 1)) {
-      c->last_kernel = coop_pairing_kernel_name(c->nl);
     } else {
-      kt->pairing(s, c->d_params, c->d_consts, Aq, Bq, E, pairs, 2, d1, d2, pairing_run(c, pairs), pws, sw, nullptr, 0,
-                  0);
-      c->last_kernel = kt->pairing_kernel_name;
+      job.window = tail ? qwin_tail : qwin_main;
+      const char* name = launch_group_pairing(c, s, q_fam, job);
+      if (!name) name = launch_lane_pairing(c, s, job);
+      c->last_kernel = name;
     }
     kt->to_mont(s, c->d_params, E.c0, E.c1, E.stride, pairs);
     PolyAccArgs pa;
@@ -2926,15 +2843,10 @@ int poly_lin_common(bgn_ctx* c, size_t npoly, size_t d, size_t dp, int level, co
   const size_t si = round_up(nin, 64), so = round_up(nout, 64);
   SoA2 A, O;
   uint8_t* kbuf = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     if (level == 1) { A = w.g1(si); O = w.g1(so); } else { A = w.gt(si); O = w.gt(so); }
     if (k_host) kbuf = (uint8_t*)w.cv.take(k_host->size());
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   if (k_host) {
     // blocking copy: the scalars live in a caller's local vector
     HIP_TRY(hipMemcpy(kbuf, k_host->data(), k_host->size(), hipMemcpyHostToDevice));
@@ -3231,8 +3143,7 @@ int field_ops_common(bgn_ctx* c, size_t count, const uint8_t* xy, uint8_t* prod_
   const size_t st = round_up(count, 64), eb = (size_t)2 * c->L * count;
   SoA2 A{}, B{}, S{};
   uint8_t *din = nullptr, *d1 = nullptr, *d2 = nullptr, *d3 = nullptr;
-  for (int pass = 0; pass < 2; ++pass) {
-    Ws w(c, pass ? c->arena : nullptr);
+  if (int rc = carve(c, [&](Ws& w) {
     A = w.gt(st);
     B = w.gt(st);
     S = w.gt(st);
@@ -3240,11 +3151,7 @@ int field_ops_common(bgn_ctx* c, size_t count, const uint8_t* xy, uint8_t* prod_
     d1 = (uint8_t*)w.cv.take(eb);
     d2 = (uint8_t*)w.cv.take(eb);
     d3 = (uint8_t*)w.cv.take(eb);
-    if (!pass) {
-      int rc = ensure_arena(c, w.cv.off);
-      if (rc) return rc;
-    }
-  }
+  })) return rc;
   if (!sums) S = SoA2{};
   HIP_TRY(hipMemcpyAsync(din, xy, eb, hipMemcpyHostToDevice, s));
   c->kt->field_ops(s, c->d_params, din, c->L, count, c->p_bits + 1, A, B, S);

@@ -7,34 +7,35 @@ namespace bgn {
 size_t coop_ws_words(int nl, size_t sw) { return (size_t)COOP_PARK_WORDS * sw + (size_t)2 * nl * sw; }
 
 template <int NL>
-static void launch(hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, SoA2 b, SoA2 out, size_t count,
-                   int mode, size_t d1, size_t d2, uint32_t* ws, size_t sw, int p_bits, const uint32_t* tab) {
+static void launch(hipStream_t s, const void* params, int p_bits, const PairingJob& j) {
   const FpParams<NL>* P = (const FpParams<NL>*)params;
+  const size_t count = j.count, sw = j.sw;
+  const int shape = (int)j.shape;
   const dim3 grid((unsigned)count), block(COOP_BLOCK);
-  if (!ws) {
-    hipLaunchKernelGGL((k_pairing_coop<NL>), grid, block, 0, s, P, consts, a, b, out, count, mode, d1, d2, 0, nullptr, nullptr,
-                       nullptr, (size_t)0, tab);
+  if (!j.ws) {
+    hipLaunchKernelGGL((k_pairing_coop<NL>), grid, block, 0, s, P, j.consts, j.a, j.b, j.out, count, shape, j.d1, j.d2, 0, nullptr,
+                       nullptr, nullptr, (size_t)0, j.tab);
     return;
   }
-  uint32_t* park = ws;
-  uint32_t* nsoa = ws + (size_t)COOP_PARK_WORDS * sw;
+  uint32_t* park = j.ws;
+  uint32_t* nsoa = j.ws + (size_t)COOP_PARK_WORDS * sw;
   uint32_t* isoa = nsoa + (size_t)NL * sw;
-  hipLaunchKernelGGL((k_pairing_coop<NL>), grid, block, 0, s, P, consts, a, b, out, count, mode, d1, d2, 1, park, nsoa, isoa, sw, tab);
+  hipLaunchKernelGGL((k_pairing_coop<NL>), grid, block, 0, s, P, j.consts, j.a, j.b, j.out, count, shape, j.d1, j.d2, 1, park, nsoa,
+                     isoa, sw, j.tab);
   hipLaunchKernelGGL((k_coop_invert<NL>), dim3((unsigned)((count + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, s, P, nsoa,
                      isoa, sw, count, p_bits);
-  hipLaunchKernelGGL((k_pairing_coop<NL>), grid, block, 0, s, P, consts, a, b, out, count, mode, d1, d2, 2, park, nsoa, isoa, sw, tab);
+  hipLaunchKernelGGL((k_pairing_coop<NL>), grid, block, 0, s, P, j.consts, j.a, j.b, j.out, count, shape, j.d1, j.d2, 2, park, nsoa,
+                     isoa, sw, j.tab);
 }
 
-bool coop_pairing_launch(int nl, hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, SoA2 b, SoA2 out,
-                         size_t count, int mode, size_t d1, size_t d2, uint32_t* ws, size_t sw, int p_bits,
-                         const uint32_t* tab) {
-  if (!count) return true;
+bool coop_pairing_launch(int nl, hipStream_t s, const void* params, int p_bits, const PairingJob& job) {
+  if (!job.count) return true;
   switch (nl) {
-    case 3: launch<3>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab); return true;
-    case 10: launch<10>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab); return true;
-    case 19: launch<19>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab); return true;
-    case 36: launch<36>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab); return true;
-    case 37: launch<37>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab); return true;
+    case 3: launch<3>(s, params, p_bits, job); return true;
+    case 10: launch<10>(s, params, p_bits, job); return true;
+    case 19: launch<19>(s, params, p_bits, job); return true;
+    case 36: launch<36>(s, params, p_bits, job); return true;
+    case 37: launch<37>(s, params, p_bits, job); return true;
   }
   return false;
 }

@@ -34,10 +34,14 @@ size_t quad_ws_words(int nl, size_t sw, int window) {
 }
 
 template <int NL>
-static void launch(hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, SoA2 b, SoA2 out, size_t total,
-                   int mode, size_t d1, size_t d2, uint32_t* ws, size_t sw_full, int p_bits, const uint32_t* tab, int window) {
+static void launch(hipStream_t s, const void* params, int p_bits, const PairingJob& j) {
   const FpParams<NL>* P = (const FpParams<NL>*)params;
-  const size_t sw = quad_ws_stride(NL, sw_full);
+  const PairingConsts* consts = j.consts;
+  const SoA2 a = j.a, b = j.b, out = j.out;
+  const size_t total = j.count, d1 = j.d1, d2 = j.d2, sw = quad_ws_stride(NL, j.sw);
+  const int shape = (int)j.shape;
+  uint32_t* ws = j.ws;
+  const uint32_t* tab = j.tab;
   auto invert = [&](uint32_t* z, uint32_t* zi, size_t stride, size_t n) {
     hipLaunchKernelGGL((k_coop_invert<NL>), dim3((unsigned)((n + FP_BLOCK - 1) / FP_BLOCK)), dim3(FP_BLOCK), 0, s, P, z, zi, stride, n,
                        p_bits);
@@ -47,7 +51,7 @@ static void launch(hipStream_t s, const void* params, const PairingConsts* const
   uint32_t* isoa = nsoa + (size_t)NL * sw;
   uint32_t* wrec = nullptr;
   uint32_t *zA = nullptr, *iA = nullptr, *z7 = nullptr, *zP = nullptr, *iP = nullptr;
-  if (window && !tab) {
+  if (j.window && !tab) {
     wrec = isoa + (size_t)NL * sw;
     zA = wrec + (size_t)QW_NV * 4 * QuadDims<NL>::M * sw;
     iA = zA + (size_t)NL * sw;
@@ -62,35 +66,33 @@ static void launch(hipStream_t s, const void* params, const PairingConsts* const
     if (wrec) {
       // the width-w loop's table: (2A, f_2), the inverse of its Z, the odd multiples and their Miller values, the
       // inverse of the product of their Z (unfolded, and the points made affine, by the Miller launch's prologue)
-      hipLaunchKernelGGL((k_pairing_quad_wtab<NL, 1>), grid, block, 0, s, P, consts, a, b, end, mode, d1, d2, wrec, zA,
+      hipLaunchKernelGGL((k_pairing_quad_wtab<NL, 1>), grid, block, 0, s, P, consts, a, b, end, shape, d1, d2, wrec, zA,
                          (const uint32_t*)nullptr, (uint32_t*)nullptr, sw, e0);
       invert(zA, iA, sw, count);
-      hipLaunchKernelGGL((k_pairing_quad_wtab<NL, 2>), grid, block, 0, s, P, consts, a, b, end, mode, d1, d2, wrec, zP,
+      hipLaunchKernelGGL((k_pairing_quad_wtab<NL, 2>), grid, block, 0, s, P, consts, a, b, end, shape, d1, d2, wrec, zP,
                          (const uint32_t*)iA, z7, sw, e0);
       invert(zP, iP, sw, count);
     }
     if (tab)
       hipLaunchKernelGGL((k_pairing_quad_table<NL>), grid, block, 0, s, P, consts, a, end, tab, park, nsoa, sw, e0);
     else
-      hipLaunchKernelGGL((k_pairing_quad<NL, 1>), grid, block, 0, s, P, consts, a, b, out, end, mode, d1, d2, park, nsoa, isoa, sw,
+      hipLaunchKernelGGL((k_pairing_quad<NL, 1>), grid, block, 0, s, P, consts, a, b, out, end, shape, d1, d2, park, nsoa, isoa, sw,
                          wrec, (const uint32_t*)iP, (const uint32_t*)z7, e0);
     invert(nsoa, isoa, sw, count);
-    hipLaunchKernelGGL((k_pairing_quad<NL, 2>), grid, block, 0, s, P, consts, a, b, out, end, mode, d1, d2, park, nsoa, isoa, sw,
+    hipLaunchKernelGGL((k_pairing_quad<NL, 2>), grid, block, 0, s, P, consts, a, b, out, end, shape, d1, d2, park, nsoa, isoa, sw,
                        (uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, e0);
   }
 }
 
-bool quad_pairing_launch(int nl, hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, SoA2 b, SoA2 out,
-                         size_t count, int mode, size_t d1, size_t d2, uint32_t* ws, size_t sw, int p_bits,
-                         const uint32_t* tab, int window) {
-  if (!count) return true;
-  if (!ws || (tab && mode != 1) || (window && (window < 3 || window > 5))) return false;
+bool quad_pairing_launch(int nl, hipStream_t s, const void* params, int p_bits, const PairingJob& job) {
+  if (!job.count) return true;
+  if (!job.ws || (job.tab && job.shape != PairShape::Broadcast) || (job.window && (job.window < 3 || job.window > 5))) return false;
   switch (nl) {
-    case 10: launch<10>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab, window); return true;
-    case 19: launch<19>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab, window); return true;
-    case 36: launch<36>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab, window); return true;
-    case 37: launch<37>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab, window); return true;
-    case 72: launch<72>(s, params, consts, a, b, out, count, mode, d1, d2, ws, sw, p_bits, tab, window); return true;
+    case 10: launch<10>(s, params, p_bits, job); return true;
+    case 19: launch<19>(s, params, p_bits, job); return true;
+    case 36: launch<36>(s, params, p_bits, job); return true;
+    case 37: launch<37>(s, params, p_bits, job); return true;
+    case 72: launch<72>(s, params, p_bits, job); return true;
   }
   return false;
 }

@@ -1,22 +1,52 @@
 // kernels.hpp — host-visible table of kernel launchers, one table per limb
 // count NL (kern_nl*.hip instantiate kernels_impl.hpp for one NL each so the
-// translation units compile in parallel).
+// translation units compile in parallel), and the argument structs they take.  A batch of pairings is described once,
+// as a PairingJob, for the lane kernel here and for the launchers of coop/coop_api.hpp and quad/quad_api.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "soa.hpp"
+
 namespace bgn {
 
 struct PairingConsts;
 
-// Device-side SoA view of `count` F_p^2-sized elements (a G1 point x,y or a GT
-// element re,im): limb j of element e at c0[j*stride + e].
-struct SoA2 {
-  uint32_t* c0;
-  uint32_t* c1;
-  uint8_t* inf;     // per-element identity flag (G1 only; may be null for GT)
-  size_t stride;
+// Which operands pairing e pairs: out[e] = e(A[ea(e)], B[eb(e)]).  The kernels of all three families receive the
+// value as an int.
+enum class PairShape : int {
+  Each = 0,         // ea = eb = e
+  Broadcast = 1,    // B is one broadcast point (b.stride == 1): ea = e, eb = 0.  With a table (PairingJob::tab) the
+                    // second operand is the key's P and the Miller loop runs over its precomputed line table
+                    // (fixedpair.hpp); b is then not read
+  Poly = 2,         // poly product: e = (q*d1 + i)*d2 + k ; ea = q*d1 + i ; eb = q*d2 + k
+  // poly product (e as in Poly) over per-coefficient line tables with limb stride tab_stride (fixedpair_build_batch);
+  // lane kernel only, and only with a table:
+  PolyTabA = 3,     // tables of the first polynomial, a = second polynomial's points, b = first polynomial (identity
+                    // flags only)
+  PolyTabB = 4,     // tables of the second polynomial, a = first polynomial's points, b = second polynomial (identity
+                    // flags only)
+};
+
+// One batch of pairings, as every family's launcher takes it (KernelTable::pairing: lane kernel; coop/coop_api.hpp:
+// cooperative kernel; quad/quad_api.hpp: lane groups).  Operands canonical Montgomery SoA, results plain canonical
+// re/im.
+struct PairingJob {
+  const PairingConsts* consts = nullptr;    // all: curve constants and the NAF of the scalar the Miller loop runs over
+  SoA2 a{}, b{};                            // all: operands (b: identity flags only, or not read, with a table)
+  SoA2 out{};                               // all
+  size_t count = 0;                         // all
+  PairShape shape = PairShape::Each;        // all (PolyTabA / PolyTabB: lane)
+  size_t d1 = 0, d2 = 0;                    // all: coefficients per polynomial, poly shapes only
+  uint32_t* ws = nullptr;                   // all: workspace, sized as each launcher says (lane, cooperative: may be null)
+  size_t sw = 0;                            // all: limb stride of the workspace arrays, >= count
+  const uint32_t* tab = nullptr;            // all: line table (cooperative, lane groups: the key's, NORMALISED, Broadcast only)
+  size_t tab_stride = 0;                    // lane: limb stride of per-coefficient tables (a key's table has stride 1)
+  bool tab_normalized = false;              // lane: the key's table holds (a/c, b/c, c) (fixedpair_normalize)
+  bool curve_a3 = false;                    // lane, no table: a and b are decoded onto the a = -3 curve (pairing.hpp miller_double)
+  int run = 1;                              // lane: pairings per lane (1 without ws)
+  int window = 0;                           // lane groups, no table: 3, 4, 5 = Miller loop over the width-w NAF of consts
 };
 
 // G1 affine addition with batched inversion (ops.hpp).
@@ -200,7 +230,7 @@ struct KernelTable {
   int nl;
   size_t params_bytes;   // sizeof(FpParams<NL>)
   const char* pairing_kernel_name;
-  const char* pairing_table_kernel_name;   // the mode-1 instantiation (walk over a key's line table)
+  const char* pairing_table_kernel_name;   // the instantiation that walks a line table (PairShape::Broadcast: a key's)
 
   // wire bytes (2L per element, big-endian) -> SoA, canonical Montgomery form.  fx / fy: null, or per-coordinate
   // factors c*R^2 mod p on the device (nl tight limbs each): x and y are stored as c_x*x*R, c_y*y*R.
@@ -213,29 +243,17 @@ struct KernelTable {
   // SoA canonical *plain* (non-Montgomery) -> wire bytes; inf != null writes zeros for identity.
   void (*encode)(hipStream_t s, const uint8_t* inf, const uint32_t* c0, const uint32_t* c1, size_t stride, int L,
                  size_t count, uint8_t* wire);
-  // out[e] = e(A[ea(e)], B[eb(e)]), plain canonical re/im.
-  //   mode 0: ea = eb = e.
-  //   mode 1: B is one broadcast point (b.stride == 1): ea = e, eb = 0.
-  //   mode 2: poly product: e = (q*d1 + i)*d2 + k ; ea = q*d1 + i ; eb = q*d2 + k.
+  // The job's pairings on the lane kernel, out plain canonical re/im.
   //   run > 1: each lane owns `run` pairings and shares one F_p inversion among them; ws = workspace of
-  //   (3 + 4 + 6*npts)*NL*sw u32 with npts = 2^(w-2) - 1 window multiples (sw >= count; 3*NL*sw suffice with fixed_tab).  run == 1 / ws == null: one pairing per lane.
+  //   (3 + 4 + 6*npts)*NL*sw u32 with npts = 2^(w-2) - 1 window multiples (sw >= count; 3*NL*sw suffice with a table).  run == 1 / ws == null: one pairing per lane.
   //   With ws != null and consts->wnaf_len > 0 the general Miller loop is the windowed one (width consts->wnaf_w).
-  //   fixed_tab != null, mode 1: the second operand is the key's P and the Miller loop runs over the
-  //   precomputed line table (fixedpair.hpp); b is ignored.
-  //   fixed_tab != null, mode 3 / 4: poly product (e as in mode 2) over per-coefficient line tables with limb
-  //   stride tab_stride (fixedpair_build_batch).  mode 3: tables of the first polynomial, a = second polynomial's
-  //   points, b = first polynomial (identity flags only); mode 4: tables of the second polynomial, a = first
-  //   polynomial's points, b = second polynomial (identity flags only).
-  void (*pairing)(hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, SoA2 b, SoA2 out,
-                  size_t count, int mode, size_t d1, size_t d2, int run, uint32_t* ws, size_t sw,
-                  const uint32_t* fixed_tab, size_t tab_stride,
-                  int variant /* bit 1 with a key table: the table is normalised; bit 2, general loop only: a and b
-                                 are decoded onto the a = -3 curve (pairing.hpp miller_double) */);
+  //   A table is walked under the shapes Broadcast, PolyTabA and PolyTabB; under Each and Poly it is not read.
+  void (*pairing)(hipStream_t s, const void* params, const PairingJob& job);
   // builds the line table of e(P, .) : 3*NL u32 per Miller step (px, py canonical Montgomery, stride 1)
   void (*fixedpair_build)(hipStream_t s, const void* params, const PairingConsts* consts, const uint32_t* px,
                           const uint32_t* py, uint32_t* tab);
   // divides every line of a key table (limb stride 1) by its c: (a, b, c) -> (a/c, b/c, c); pfx = scratch of
-  // steps*NL u32.  A normalised table is used by passing variant = 2 to `pairing` (mode 1).
+  // steps*NL u32.  A normalised table is used by setting PairingJob::tab_normalized (shape Broadcast).
   void (*fixedpair_normalize)(hipStream_t s, const void* params, uint32_t* tab, size_t steps, uint32_t* pfx, int p_bits);
   // one line table per point of a[0..count): value v of step s, limb j, point I at tab[((3*s+v)*NL + j)*ts + I]
   void (*fixedpair_build_batch)(hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, size_t count,

@@ -826,21 +826,19 @@ static void launch_encode(hipStream_t s, const uint8_t* inf, const uint32_t* c0,
   hipLaunchKernelGGL(k_encode<NL_>, dim3(grid_for(count)), dim3(FP_BLOCK), 0, s, inf, c0, c1, stride, L, count, wire);
 }
 
-static void launch_pairing(hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, SoA2 b, SoA2 out,
-                           size_t count, int mode, size_t d1, size_t d2, int run, uint32_t* ws, size_t sw,
-                           const uint32_t* fixed_tab, size_t tab_stride, int variant) {
-  if (!count) return;
-  if (run < 1 || !ws) run = 1;
-  const size_t lanes = (count + run - 1) / run;
-  // variant bit 1 (value 2) with a key table: the table is normalised (fixed_normalize_lane); bit 2 (value 4): curve_a3
-  if (fixed_tab && (mode == 1 || mode >= 3))
+static void launch_pairing(hipStream_t s, const void* params, const PairingJob& j) {
+  if (!j.count) return;
+  const int run = (j.run < 1 || !j.ws) ? 1 : j.run;
+  const size_t lanes = (j.count + run - 1) / run;
+  const bool key_tab = j.shape == PairShape::Broadcast;      // one table of limb stride 1, perhaps normalised
+  if (j.tab && (key_tab || j.shape == PairShape::PolyTabA || j.shape == PairShape::PolyTabB))
     hipLaunchKernelGGL((k_pairing<NL_, 1>), dim3(grid_for(lanes)), dim3(FP_BLOCK), 0, s,
-                       (const FpParams<NL_>*)params, consts, a, b, out, count, mode, d1, d2, run, ws, sw, fixed_tab,
-                       mode == 1 ? (size_t)1 : tab_stride, (mode == 1 && (variant & 2)) ? 1 : 0, 0);
+                       (const FpParams<NL_>*)params, j.consts, j.a, j.b, j.out, j.count, (int)j.shape, j.d1, j.d2, run, j.ws,
+                       j.sw, j.tab, key_tab ? (size_t)1 : j.tab_stride, (key_tab && j.tab_normalized) ? 1 : 0, 0);
   else
     hipLaunchKernelGGL((k_pairing<NL_, 0>), dim3(grid_for(lanes)), dim3(FP_BLOCK), 0, s,
-                       (const FpParams<NL_>*)params, consts, a, b, out, count, mode, d1, d2, run, ws, sw, nullptr,
-                       (size_t)0, 0, (variant & 4) ? 1 : 0);
+                       (const FpParams<NL_>*)params, j.consts, j.a, j.b, j.out, j.count, (int)j.shape, j.d1, j.d2, run, j.ws,
+                       j.sw, nullptr, (size_t)0, 0, j.curve_a3 ? 1 : 0);
 }
 
 template <int NL>

@@ -3,19 +3,19 @@
 #include "../kernels.hpp"
 
 namespace bgn {
-// out[e] = e(a[e], b[e]) (mode 0), e(a[e], b[0]) (mode 1) or the coefficient pairs of MultPoly (mode 2, as
-// KernelTable::pairing) for e < count, sixteen lanes per pairing; operands canonical Montgomery SoA, results plain
-// canonical SoA, as KernelTable::pairing.  ws: workspace of quad_ws_words(nl, sw) u32 (sw >= count, the limb stride
-// of its arrays): Miller-loop launch, batched inversion of the norms (k_coop_invert, one per lane),
-// final-exponentiation launch.  Returns false when `nl` has no instantiation (then nothing was launched).
-// tab != nullptr (mode 1 only): e(K, a[e]) over the NORMALISED line table of the key point K (fixedpair.hpp; limb
-// stride 1) built for the scalar whose NAF `consts` holds; b is not read.
-// window = 3, 4, 5 (general pairings only, tab == nullptr): the Miller loop over the width-w NAF that `consts` holds
+// The job's pairings (kernels.hpp PairingJob; shapes Each, Broadcast and Poly), sixteen lanes per pairing; operands
+// canonical Montgomery SoA, results plain canonical SoA, as KernelTable::pairing.  job.ws: workspace of
+// quad_ws_words(nl, sw) u32 (sw >= count, the limb stride of its arrays): Miller-loop launch, batched inversion of the
+// norms (k_coop_invert, one per lane; p_bits bounds the bit length of p for its division steps),
+// final-exponentiation launch.  Returns false when `nl` has no instantiation or the job cannot be served — no
+// workspace, a table under another shape than Broadcast, a window outside 3 .. 5 — (then nothing was launched).
+// job.tab != nullptr (Broadcast only): e(K, a[e]) over the NORMALISED line table of the key point K (fixedpair.hpp; limb
+// stride 1) built for the scalar whose NAF job.consts holds; b is not read.
+// job.window = 3, 4, 5 (general pairings only, no table): the Miller loop over the width-w NAF that job.consts holds
 // (wnaf, wnaf_w == window) with a per-pairing table of the odd multiples of a[e] and their Miller values — two table
 // launches and two more inversion launches in front of the Miller launch; ws then has quad_ws_words(nl, sw, window) words.
-bool quad_pairing_launch(int nl, hipStream_t s, const void* params, const PairingConsts* consts, SoA2 a, SoA2 b, SoA2 out,
-                         size_t count, int mode, size_t d1, size_t d2, uint32_t* ws, size_t sw, int p_bits,
-                         const uint32_t* tab = nullptr, int window = 0);
+// Not read: tab_stride, tab_normalized, curve_a3, run.
+bool quad_pairing_launch(int nl, hipStream_t s, const void* params, int p_bits, const PairingJob& job);
 // out[e] = a[e]^k in F_p^2, ONE exponent for all elements (k big-endian, klen <= 256 bytes), sixteen lanes per element;
 // a, out canonical Montgomery SoA (limb strides sa, so; sa == 1 — one base for all — is not served: false).
 bool quad_gt_pow_launch(int nl, hipStream_t s, const void* params, const uint32_t* a0, const uint32_t* a1, size_t sa,
