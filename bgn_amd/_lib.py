@@ -52,6 +52,13 @@ PROTOTYPES = {
     "bgn_validate_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, C.c_void_p]),
     "bgn_check_decryption_proof_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p, _sz, _u8p, _sz, _u8p]),
     "bgn_check_plaintext_knowledge_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _sz, _u8p, _sz, _u8p]),
+    "bgn_challenge_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p]),
+    "bgn_prove_plaintext_knowledge_batch": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, _sz, _u8p, _sz, _u8p, _sz, _u8p, _u8p, _u8p]),
+    "bgn_verify_plaintext_knowledge_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _u8p, _sz, _u8p]),
+    "bgn_challenge_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, C.c_void_p]),
+    "bgn_prove_plaintext_knowledge_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, _sz, _u8p, _sz, _u8p, _sz, _u8p, _u8p, _u8p,
+                                                          C.c_void_p]),
+    "bgn_verify_plaintext_knowledge_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_encrypt_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_add_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_sub_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),

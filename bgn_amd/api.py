@@ -322,6 +322,80 @@ class Engine:
         check(self._lib.bgn_poly_eval_batch_dev(self._h, npoly, d, level, ct.data_ptr(), base, out.data_ptr(),
                                                 self._stream()), "bgn_poly_eval_batch_dev")
 
+    # ---- proofs of plaintext knowledge (gadgets.go:32-96), the hash on the device -------------------------------
+    @property
+    def n_len(self) -> int:
+        """Bytes of the group order: the row length of the responses (DL) of bgn_prove_plaintext_knowledge_batch."""
+        return (self.n.bit_length() + 7) // 8
+
+    def challenge(self, ct: BytesLike, nonce: BytesLike) -> np.ndarray:
+        """sha256(ct[i] || nonce[i]): count x 32 digest bytes (hash(), gadgets.go:80-96)."""
+        A, B = _as_u8(ct, self.elem_bytes), _as_u8(nonce, self.elem_bytes)
+        if len(A) != len(B):
+            raise ValueError("operand counts differ")
+        out = np.zeros((len(A), 32), dtype=np.uint8)
+        check(self._lib.bgn_challenge_batch(self._h, len(A), _ptr(A), _ptr(B), _ptr(out)), "bgn_challenge_batch")
+        return out
+
+    def prove_plaintext_knowledge(self, v: Sequence[int], z: Sequence[int], nonce1: Sequence[int], rq: int):
+        """(ct, nonce, dl) rows of the proofs for plaintexts v, randomness z and nonces nonce1 (all below 2^(8 n_len));
+        rq = R * (n / q1) mod n.  NewProofOfPlaintextKnowledge, gadgets.go:32-54."""
+        vs, zs, ns = _scalars(v), _scalars(z), _scalars(nonce1)
+        if not (len(vs) == len(zs) == len(ns)):
+            raise ValueError("operand counts differ")
+        k = _scalars([rq])
+        ct, nonce = self._out(len(vs)), self._out(len(vs))
+        dl = np.zeros((len(vs), self.n_len), dtype=np.uint8)
+        check(self._lib.bgn_prove_plaintext_knowledge_batch(self._h, len(vs), _ptr(vs), vs.shape[1], _ptr(zs), zs.shape[1],
+                                                            _ptr(ns), ns.shape[1], _ptr(k), k.shape[1], _ptr(ct),
+                                                            _ptr(nonce), _ptr(dl)), "bgn_prove_plaintext_knowledge_batch")
+        return ct, nonce, dl
+
+    def verify_plaintext_knowledge(self, ct: BytesLike, proof_ct: BytesLike, nonce: BytesLike, dl: Sequence[int]) -> np.ndarray:
+        """1 per proof (proof_ct, nonce, dl) that holds for the ciphertext under test ct
+        (CheckProofOfPlaintextKnoewledge, gadgets.go:65-77), the challenge computed on the device."""
+        A, PC, N = (_as_u8(x, self.elem_bytes) for x in (ct, proof_ct, nonce))
+        d = _scalars(dl)
+        if not (len(A) == len(PC) == len(N) == len(d)):
+            raise ValueError("operand counts differ")
+        ok = np.zeros(len(A), dtype=np.uint8)
+        check(self._lib.bgn_verify_plaintext_knowledge_batch(self._h, len(A), _ptr(A), _ptr(PC), _ptr(N), _ptr(d), d.shape[1],
+                                                             _ptr(ok)), "bgn_verify_plaintext_knowledge_batch")
+        return ok
+
+    def challenge_dev(self, ct, nonce, out, count: Optional[int] = None) -> None:
+        """Device-resident challenge: out = count x 32 bytes.  The arrays may start at any byte address."""
+        count = ct.numel() // self.elem_bytes if count is None else count
+        self._need("ct", ct, count * self.elem_bytes)
+        self._need("nonce", nonce, count * self.elem_bytes)
+        self._need("out", out, count * 32)
+        check(self._lib.bgn_challenge_batch_dev(self._h, count, ct.data_ptr(), nonce.data_ptr(), out.data_ptr(),
+                                                self._stream()), "bgn_challenge_batch_dev")
+
+    def prove_plaintext_knowledge_dev(self, v, v_len: int, z, z_len: int, nonce1, nonce1_len: int, rq, rq_len: int,
+                                      ct_out, nonce_out, dl_out, count: int) -> None:
+        """Device-resident Prove: big-endian scalar rows in, ciphertexts, nonces and responses (n_len bytes each) out;
+        rq: the rq_len bytes of R * (n / q1) mod n on the device."""
+        for what, t, w in (("v", v, v_len), ("z", z, z_len), ("nonce1", nonce1, nonce1_len), ("ct_out", ct_out, self.elem_bytes),
+                           ("nonce_out", nonce_out, self.elem_bytes), ("dl_out", dl_out, self.n_len)):
+            self._need(what, t, count * w)
+        self._need("rq", rq, rq_len)
+        check(self._lib.bgn_prove_plaintext_knowledge_batch_dev(self._h, count, v.data_ptr(), v_len, z.data_ptr(), z_len,
+                                                                nonce1.data_ptr(), nonce1_len, rq.data_ptr(), rq_len,
+                                                                ct_out.data_ptr(), nonce_out.data_ptr(), dl_out.data_ptr(),
+                                                                self._stream()), "bgn_prove_plaintext_knowledge_batch_dev")
+
+    def verify_plaintext_knowledge_dev(self, ct, proof_ct, nonce, dl, dl_len: int, ok, count: Optional[int] = None) -> None:
+        """Device-resident Verify: nothing of the proofs is downloaded."""
+        count = ct.numel() // self.elem_bytes if count is None else count
+        for what, t in (("ct", ct), ("proof_ct", proof_ct), ("nonce", nonce)):
+            self._need(what, t, count * self.elem_bytes)
+        self._need("dl", dl, count * dl_len)
+        self._need("ok", ok, count)
+        check(self._lib.bgn_verify_plaintext_knowledge_batch_dev(self._h, count, ct.data_ptr(), proof_ct.data_ptr(),
+                                                                 nonce.data_ptr(), dl.data_ptr(), dl_len, ok.data_ptr(),
+                                                                 self._stream()), "bgn_verify_plaintext_knowledge_batch_dev")
+
     def field_ops(self, xy: BytesLike):
         """Diagnostics: (x*y || 1/x, x^2 || y^2) for elements x||y of plain residues (bgn_field_ops_batch)."""
         A = _as_u8(xy, self.elem_bytes)
@@ -833,18 +907,27 @@ class PublicKey:
         return Ciphertext(bytes(self._blind(out, ct.L2)[0]), ct.L2)
 
     # -- proofs: gadgets.go --
-    def _hash(self, ct_bytes: bytes, nonce_bytes: bytes) -> int:
-        import hashlib
-        return int.from_bytes(hashlib.sha256(bytes(ct_bytes) + bytes(nonce_bytes)).digest(), "big")   # gadgets.go:80-96
+    def NewProofOfPlaintextKnowledgeBatch(self, sk: "SecretKey", vs: Sequence[int], zs: Sequence[int],
+                                          nonce1s: Optional[Sequence[int]] = None) -> List["ProofOfPlaintextKnowledge"]:
+        """gadgets.go:32-54 for a batch, in one engine call: both encryptions, the hash and the response
+        DL = r + c*v + R*z*c*(N/Key) mod N run on the device.  The per-key factor R*(N/Key) mod N is computed here
+        once; missing nonces are drawn here (`nonce1s` may be supplied to make the proofs reproducible)."""
+        vs, zs = [int(v) % self.N for v in vs], [int(z) % self.N for z in zs]      # (as EncryptBatch: P^(x mod n))
+        if len(vs) != len(zs):
+            raise ValueError("operand counts differ")
+        if nonce1s is None:
+            nonce1s = [secrets.randbelow(self.N) for _ in vs]                      # newCryptoRandom, gadgets.go:33
+        nonce1s = [int(a) % self.N for a in nonce1s]
+        if not vs:
+            return []
+        rq = sk.R * (self.N // sk.Key) % self.N
+        ct, nonce, dl = self.engine.prove_plaintext_knowledge(vs, zs, nonce1s, rq)
+        return [ProofOfPlaintextKnowledge(Ciphertext(bytes(c), False), Ciphertext(bytes(a), False),
+                                          int.from_bytes(bytes(d), "big")) for c, a, d in zip(ct, nonce, dl)]
 
     def NewProofOfPlaintextKnowledge(self, sk: "SecretKey", v: int, z: int, nonce1: Optional[int] = None):
-        """gadgets.go:32-54 (`nonce1` may be supplied to make the proof reproducible)."""
-        if nonce1 is None:
-            nonce1 = secrets.randbelow(self.N)
-        ct, nonce = self.EncryptBatch([v, nonce1], [z, 0])
-        nonce2 = self._hash(ct.C, nonce.C)
-        DL = (nonce1 + nonce2 * v + sk.R * z * nonce2 * (self.N // sk.Key)) % self.N
-        return ProofOfPlaintextKnowledge(ct, nonce, DL)
+        """gadgets.go:32-54 (`nonce1` may be supplied to make the proof reproducible): the batch of one."""
+        return self.NewProofOfPlaintextKnowledgeBatch(sk, [v], [z], None if nonce1 is None else [nonce1])[0]
 
     def CheckDecryptionProofBatch(self, cts: Sequence[Ciphertext], proofs: Sequence["DecryptionProof"]) -> List[bool]:
         if not cts:
@@ -865,15 +948,9 @@ class PublicKey:
                                              proofs: Sequence["ProofOfPlaintextKnowledge"]) -> List[bool]:
         if not cts:
             return []
-        E = self.engine.elem_bytes
-        c = _scalars([self._hash(pr.Ct.C, pr.Nonce.C) for pr in proofs], 32)   # nonce2 := hash(proof), gadgets.go:67
-        dl = _scalars([pr.DL for pr in proofs])
-        a = _as_u8(b"".join(x.C for x in cts), E)
-        nn = _as_u8(b"".join(pr.Nonce.C for pr in proofs), E)
-        ok = np.zeros(len(cts), dtype=np.uint8)
-        check(self.engine._lib.bgn_check_plaintext_knowledge_batch(self.engine._h, len(cts), _ptr(a), _ptr(nn), _ptr(c), 32,
-                                                                   _ptr(dl), dl.shape[1], _ptr(ok)),
-              "bgn_check_plaintext_knowledge_batch")
+        # nonce2 := hash(proof) (gadgets.go:67) is computed on the device, from the proof's own Ct and Nonce
+        ok = self.engine.verify_plaintext_knowledge(b"".join(x.C for x in cts), b"".join(pr.Ct.C for pr in proofs),
+                                                    b"".join(pr.Nonce.C for pr in proofs), [pr.DL for pr in proofs])
         return [bool(x) for x in ok]
 
     def CheckProofOfPlaintextKnoewledge(self, ct: Ciphertext, proof: "ProofOfPlaintextKnowledge") -> bool:

@@ -57,6 +57,8 @@ int fail(int code, const char* fmt, ...) {
 
 size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+constexpr size_t POK_CHALLENGE_BYTES = 32;     // a sha256 digest (kernels.hpp KernelTable::challenge)
+
 // the elements of v from `off` on
 SoA2 view(SoA2 v, size_t off) {
   v.c0 += off;
@@ -109,6 +111,8 @@ struct bgn_ctx {
 
   void* d_params = nullptr;            // FpParams<NL>
   void* d_barrett = nullptr;           // BarrettParams<NL> (barrett.hpp); null: the fused level-2 Add / Sub is not offered
+  void* d_params_n = nullptr;          // FpParams<NL> with the group order n for the modulus: proof responses (proofs.hpp)
+  size_t n_len = 0;                    // bytes of n
   bool stream_codec = false;           // codec.hpp StreamCodec<NL>::serves(L): the fused Add / Sub kernels decode and encode with it only
   PairingConsts* d_consts = nullptr;
   uint32_t* d_keypts = nullptr;        // P.x, P.y, Q.x, Q.y, eQQ.re, eQQ.im, one, zero : 8 * nl limbs, stride 1, Montgomery
@@ -471,6 +475,7 @@ void bgn_ctx_destroy(bgn_ctx* c) {
   if (c->poly_tab) (void)ctx_free(c, c->poly_tab);
   if (c->d_params) (void)ctx_free(c, c->d_params);
   if (c->d_barrett) (void)ctx_free(c, c->d_barrett);
+  if (c->d_params_n) (void)ctx_free(c, c->d_params_n);
   if (c->d_consts) (void)ctx_free(c, c->d_consts);
   if (c->d_a3) (void)ctx_free(c, c->d_a3);
   if (c->d_keypts) (void)ctx_free(c, c->d_keypts);
@@ -552,6 +557,14 @@ int bgn_ctx_create(bgn_ctx** out, const uint8_t* p_be, size_t p_len, const uint8
   }
     HIP_BRK(ctx_malloc(c, (void**)&c->d_params, kt->params_bytes));
     HIP_BRK(hipMemcpy(c->d_params, img.data(), kt->params_bytes, hipMemcpyHostToDevice));
+    {
+      // the same block for the group order (odd, below p): one, r2, kp[] and pinv of n — arithmetic modulo n of the
+      // proof responses runs on the Montgomery row product unchanged (proofs.hpp)
+      const std::vector<uint32_t> nimg = build_params(n, c->nl);
+      c->n_len = ((size_t)n.bits() + 7) / 8;
+      HIP_BRK(ctx_malloc(c, (void**)&c->d_params_n, kt->params_bytes));
+      HIP_BRK(hipMemcpy(c->d_params_n, nimg.data(), kt->params_bytes, hipMemcpyHostToDevice));
+    }
     // (the fused kernel decodes and encodes with the dword-stream codec only: codec.hpp StreamCodec<NL>::serves)
     const int nd = (LIMB_BITS * c->nl + 31) / 32, full = c->L >> 2;
     c->stream_codec = c->L >= 4 && full >= (nd > 4 ? nd - 4 : 0) && full <= nd;
@@ -2974,6 +2987,138 @@ int bgn_check_plaintext_knowledge_batch_dev(bgn_ctx* c, size_t count, const uint
   if ((rc = wire_equal(c, (hipStream_t)stream, a, b, count, ok))) return rc;
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return BGN_OK;
+}
+
+// ---- proofs of plaintext knowledge without a host hash (gadgets.go:32-96) ---------------------------------------------
+// The challenge sha256(Ct || Nonce) is computed where the two arrays are (k_challenge), so a device-resident batch is
+// proved and verified without its bytes leaving the device.  Verify is k_challenge in front of the chain of
+// bgn_check_plaintext_knowledge_batch_dev; Prove is Encrypt(v, z), Encrypt(nonce1), k_challenge, k_pok_response on one
+// stream.  Both own a scratch array of challenges and synchronise the stream before they return, like the checks above.
+namespace {
+int challenge_launch(bgn_ctx* c, hipStream_t s, size_t count, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  c->kt->challenge(s, a, b, 2 * (size_t)c->L, count, out);
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->ev_valid = true;
+  c->last_kernel = "k_challenge";
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+}  // namespace
+
+int bgn_challenge_batch_dev(bgn_ctx* c, size_t count, const uint8_t* ct, const uint8_t* nonce, uint8_t* c_out, void* stream) {
+  if (!c || (count && (!ct || !nonce || !c_out))) return fail(BGN_E_ARG, "null argument");
+  if (!count) return BGN_OK;
+  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  HIP_TRY(hipSetDevice(c->device));
+  return challenge_launch(c, (hipStream_t)stream, count, ct, nonce, c_out);
+}
+
+int bgn_verify_plaintext_knowledge_batch_dev(bgn_ctx* c, size_t count, const uint8_t* ct, const uint8_t* proof_ct,
+                                             const uint8_t* nonce, const uint8_t* dl_be, size_t dl_len, uint8_t* ok,
+                                             void* stream) {
+  if (!c || (count && (!ct || !proof_ct || !nonce || !dl_be || !ok))) return fail(BGN_E_ARG, "null argument");
+  if (!dl_len) return fail(BGN_E_ARG, "zero scalar length");
+  if (!count) return BGN_OK;
+  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  HIP_TRY(hipSetDevice(c->device));
+  DevBuf ch;
+  int rc;
+  if ((rc = ch.alloc(count * POK_CHALLENGE_BYTES))) return rc;
+  // nonce2 := hash(proof): the proof's own Ct and Nonce (gadgets.go:67, :80-96)
+  if ((rc = challenge_launch(c, (hipStream_t)stream, count, proof_ct, nonce, (uint8_t*)ch.p))) return rc;
+  // the check itself, on the ciphertext under test (gadgets.go:69-76); it synchronises the stream before it returns
+  return bgn_check_plaintext_knowledge_batch_dev(c, count, ct, nonce, (const uint8_t*)ch.p, POK_CHALLENGE_BYTES, dl_be, dl_len,
+                                                 ok, stream);
+}
+
+namespace {
+int prove_args(const bgn_ctx* c, size_t count, const void* v, size_t v_len, const void* z, size_t z_len, const void* a,
+               size_t a_len, const void* rq, size_t rq_len, const void* ct, const void* nonce, const void* dl) {
+  if (!c) return fail(BGN_E_ARG, "null argument");
+  if (!v_len || !z_len || !a_len || !rq_len) return fail(BGN_E_ARG, "zero scalar length");
+  if (v_len > c->n_len || z_len > c->n_len || a_len > c->n_len || rq_len > c->n_len)
+    return fail(BGN_E_ARG, "scalar longer than the group order (%zu bytes)", c->n_len);
+  if (count && (!v || !z || !a || !rq || !ct || !nonce || !dl)) return fail(BGN_E_ARG, "null argument");
+  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  return BGN_OK;
+}
+}  // namespace
+
+int bgn_prove_plaintext_knowledge_batch_dev(bgn_ctx* c, size_t count, const uint8_t* v_be, size_t v_len, const uint8_t* z_be,
+                                            size_t z_len, const uint8_t* nonce1_be, size_t nonce1_len, const uint8_t* rq_be,
+                                            size_t rq_len, uint8_t* ct_out, uint8_t* nonce_out, uint8_t* dl_out, void* stream) {
+  if (int rc = prove_args(c, count, v_be, v_len, z_be, z_len, nonce1_be, nonce1_len, rq_be, rq_len, ct_out, nonce_out, dl_out))
+    return rc;
+  if (!count) return BGN_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  DevBuf ch;
+  int rc;
+  if ((rc = ch.alloc(count * POK_CHALLENGE_BYTES))) return rc;
+  // ct := pk.EncryptWithRandomness(v, z); nonce := pk.EncryptWithRandomness(r, 0)          (gadgets.go:34-39)
+  if ((rc = bgn_encrypt_batch_dev(c, count, v_be, v_len, z_be, z_len, ct_out, stream))) return rc;
+  if ((rc = bgn_encrypt_batch_dev(c, count, nonce1_be, nonce1_len, nullptr, 0, nonce_out, stream))) return rc;
+  // nonce2 := hash(proof)                                                                 (gadgets.go:41)
+  if ((rc = challenge_launch(c, s, count, ct_out, nonce_out, (uint8_t*)ch.p))) return rc;
+  {
+    // DL = r + nonce2*v + R*z*nonce2*(N/Key) mod N                                        (gadgets.go:42-49)
+    std::lock_guard<std::mutex> lk(c->mu);
+    PokArgs a{v_be, v_len, z_be, z_len, nonce1_be, nonce1_len, (const uint8_t*)ch.p, rq_be, rq_len, dl_out, c->n_len, count};
+    HIP_TRY(hipEventRecord(c->ev0, s));
+    c->kt->pok_response(s, c->d_params_n, a);
+    HIP_TRY(hipEventRecord(c->ev1, s));
+    c->ev_valid = true;
+    c->last_kernel = "k_pok_response";
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(s));                         // the scratch array is freed on return
+  return BGN_OK;
+}
+
+int bgn_challenge_batch(bgn_ctx* c, size_t count, const uint8_t* ct, const uint8_t* nonce, uint8_t* c_out) {
+  if (!c || (count && (!ct || !nonce || !c_out))) return fail(BGN_E_ARG, "null argument");
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0, {{ct, nullptr, E, count}, {nonce, nullptr, E, count}, {nullptr, c_out, POK_CHALLENGE_BYTES, count}},
+                   [&](size_t n, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_challenge_batch_dev(c, n, in[0], in[1], o[0], s);
+                   });
+}
+
+int bgn_prove_plaintext_knowledge_batch(bgn_ctx* c, size_t count, const uint8_t* v_be, size_t v_len, const uint8_t* z_be,
+                                        size_t z_len, const uint8_t* nonce1_be, size_t nonce1_len, const uint8_t* rq_be,
+                                        size_t rq_len, uint8_t* ct_out, uint8_t* nonce_out, uint8_t* dl_out) {
+  if (int rc = prove_args(c, count, v_be, v_len, z_be, z_len, nonce1_be, nonce1_len, rq_be, rq_len, ct_out, nonce_out, dl_out))
+    return rc;
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0,
+                   {{v_be, nullptr, v_len, count}, {z_be, nullptr, z_len, count}, {nonce1_be, nullptr, nonce1_len, count},
+                    {rq_be, nullptr, rq_len, 1}, {nullptr, ct_out, E, count}, {nullptr, nonce_out, E, count},
+                    {nullptr, dl_out, c->n_len, count}},
+                   [&](size_t n, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     const int rc = bgn_prove_plaintext_knowledge_batch_dev(c, n, in[0], v_len, in[1], z_len, in[2], nonce1_len,
+                                                                            in[3], rq_len, o[0], o[1], o[2], s);
+                     // the staged copy of the per-key factor does not outlive the call (staging buffers are pooled)
+                     if (rc == BGN_OK) HIP_TRY(hipMemsetAsync(in[3], 0, rq_len, s));
+                     return rc;
+                   });
+}
+
+int bgn_verify_plaintext_knowledge_batch(bgn_ctx* c, size_t count, const uint8_t* ct, const uint8_t* proof_ct,
+                                         const uint8_t* nonce, const uint8_t* dl_be, size_t dl_len, uint8_t* ok) {
+  if (!c || (count && (!ct || !proof_ct || !nonce || !dl_be || !ok))) return fail(BGN_E_ARG, "null argument");
+  if (!dl_len) return fail(BGN_E_ARG, "zero scalar length");
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0,
+                   {{ct, nullptr, E, count}, {proof_ct, nullptr, E, count}, {nonce, nullptr, E, count},
+                    {dl_be, nullptr, dl_len, count}, {nullptr, ok, 1, count}},
+                   [&](size_t n, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_verify_plaintext_knowledge_batch_dev(c, n, in[0], in[1], in[2], in[3], dl_len, o[0], s);
+                   });
 }
 
 // ---- calibration of the batch-size crossovers ----------------------------------------------------------------------

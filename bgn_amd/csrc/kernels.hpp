@@ -226,6 +226,18 @@ struct PolyLinArgs {
   int nbits;                                                                // scalar bits to scan (<= 8*klen)
 };
 
+// The response of a proof of plaintext knowledge (proofs.hpp): dl[e] = (a[e] + c[e] * (v[e] + K * z[e])) mod n.
+// Unsigned big-endian rows; the lengths are at most n_len, the challenge rows 32 bytes; k is ONE scalar for the batch.
+struct PokArgs {
+  const uint8_t* v; size_t v_len;
+  const uint8_t* z; size_t z_len;
+  const uint8_t* a; size_t a_len;                                           // nonce1
+  const uint8_t* c;                                                         // challenges, 32 bytes each
+  const uint8_t* k; size_t k_len;                                           // K = R * (n / q1) mod n
+  uint8_t* dl; size_t n_len;                                                // canonical residues, n_len bytes each
+  size_t count;
+};
+
 struct KernelTable {
   int nl;
   size_t params_bytes;   // sizeof(FpParams<NL>)
@@ -310,9 +322,13 @@ struct KernelTable {
   void (*gt_mul_wire)(hipStream_t s, const void* params, const void* barrett, const uint8_t* a, const uint8_t* b, int L,
                       size_t count, int conj_b, uint8_t* out);
   const void* gt_mul_wire_entry;      // the kernel's host-side handle (hipFuncGetAttributes: bgn_last_kernel_resources)
+  // out[e] = sha256(a[e] || b[e]) for elements of len_each bytes at any byte address, 32 digest bytes each (sha256.hpp)
+  void (*challenge)(hipStream_t s, const uint8_t* a, const uint8_t* b, size_t len_each, size_t count, uint8_t* out);
+  // proof responses modulo n; params_n = FpParams<NL> with n for the modulus (engine.cpp build_params(n))
+  void (*pok_response)(hipStream_t s, const void* params_n, PokArgs a);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
-  Entry entries[12];
+  Entry entries[14];
 };
 
 const KernelTable* kernel_table_nl3();

@@ -8,6 +8,8 @@
 #include "fixedpair.hpp"
 #include "polyops.hpp"
 #include "barrett.hpp"
+#include "sha256.hpp"
+#include "proofs.hpp"
 
 namespace bgn {
 
@@ -1217,6 +1219,44 @@ static void launch_pairing_multi(hipStream_t s, const void* params, const Pairin
                      (const FpParams<NL_>*)params, consts, V, tinf, out, nq, Qp, d, tab, ts);
 }
 
+// ---- proofs of plaintext knowledge (gadgets.go:32-96) ----------------------------------------------------------------
+// The Fiat-Shamir challenge: out[e] = sha256(a[e] || b[e]), one proof per lane, elements of len_each bytes at any byte
+// address.  Nothing of the limb count enters (NL only names the instantiation of this translation unit); no LDS, no
+// scratch: 16 schedule words, 8 state words and the addresses.
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_challenge(const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, size_t len_each, size_t count,
+            uint8_t* __restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  if (e >= count) return;
+  u32 st[8];
+  sha256_wire(a + e * len_each, b + e * len_each, len_each, st);
+  sha256_store(out + e * 32, st);
+}
+
+static void launch_challenge(hipStream_t s, const uint8_t* a, const uint8_t* b, size_t len_each, size_t count, uint8_t* out) {
+  if (!count) return;
+  hipLaunchKernelGGL(k_challenge<NL_>, dim3(grid_for(count)), dim3(FP_BLOCK), 0, s, a, b, len_each, count, out);
+}
+
+// The response: dl[e] = (nonce1[e] + c[e] * (v[e] + K * z[e])) mod n over the parameter block of n (proofs.hpp).  One
+// proof per lane; the operands are secrets — every lane runs the same instructions on the same addresses pattern
+// (row e of each array), whatever the values.
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_pok_response(const FpParams<NL>* __restrict__ N, PokArgs A) {
+  __shared__ LFp<NL> stage;
+  const size_t e = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  if (e >= A.count) return;
+  pok_response_bytes<NL>(A.dl + e * A.n_len, (int)A.n_len, A.v + e * A.v_len, (int)A.v_len, A.z + e * A.z_len, (int)A.z_len,
+                         A.a + e * A.a_len, (int)A.a_len, A.c + e * POK_C_BYTES, A.k, (int)A.k_len, N, &stage);
+}
+
+static void launch_pok_response(hipStream_t s, const void* params_n, PokArgs a) {
+  if (!a.count) return;
+  hipLaunchKernelGGL(k_pok_response<NL_>, dim3(grid_for(a.count)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params_n, a);
+}
+
 const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
   static const KernelTable t = {
       NL_,
@@ -1264,6 +1304,8 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
       nullptr,              // 72 limbs: the fully unrolled products would be 50 k instructions; the four-launch route serves
       nullptr,
 #endif
+      launch_challenge,
+      launch_pok_response,
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1276,6 +1318,8 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
        {"k_g1_mul", (const void*)k_g1_mul<NL_>},
        {"k_gt_pow", (const void*)k_gt_pow<NL_>},
        {"k_g1_fixed_chain", (const void*)k_g1_fixed_chain<NL_>},
+       {"k_challenge", (const void*)k_challenge<NL_>},
+       {"k_pok_response", (const void*)k_pok_response<NL_>},
        {nullptr, nullptr}},
   };
   return &t;

@@ -490,8 +490,8 @@ func (e *Engine) CheckDecryptionProofBatch(cts []*Ciphertext, proofs []*Decrypti
 	return bools(ok), nil
 }
 
-// CheckPlaintextKnowledgeBatch is pk.CheckProofOfPlaintextKnoewledge (gadgets.go:65-77) over arrays: hash()
-// (gadgets.go:80-96) stays in Go.
+// CheckPlaintextKnowledgeBatch is pk.CheckProofOfPlaintextKnoewledge (gadgets.go:65-77) over arrays with hash()
+// (gadgets.go:80-96) computed in Go; VerifyPlaintextKnowledgeBatch below computes it on the device.
 func (e *Engine) CheckPlaintextKnowledgeBatch(cts []*Ciphertext, proofs []*ProofOfPlaintextKnowledge) ([]bool, error) {
 	A := e.pack(cts)
 	N := make([]byte, 0, len(A))
@@ -506,6 +506,106 @@ func (e *Engine) CheckPlaintextKnowledgeBatch(cts []*Ciphertext, proofs []*Proof
 	ok := make([]uint8, len(cts))
 	err := locked(func() C.int {
 		return C.bgn_check_plaintext_knowledge_batch(e.h, C.size_t(len(cts)), u8(A), u8(N), u8(c), 32, u8(dl), C.size_t(dw), u8(ok))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return bools(ok), nil
+}
+
+// ChallengeBatch is hash() (gadgets.go:80-96) over arrays, on the device: 32 digest bytes per pair
+// (bgn_challenge_batch).
+func (e *Engine) ChallengeBatch(cts, nonces []*Ciphertext) ([][]byte, error) {
+	if len(cts) != len(nonces) {
+		return nil, errors.New("bgn_amd: ChallengeBatch takes as many nonces as ciphertexts")
+	}
+	if len(cts) == 0 {
+		return nil, nil
+	}
+	A, B := e.pack(cts), e.pack(nonces)
+	c := make([]byte, 32*len(cts))
+	err := locked(func() C.int { return C.bgn_challenge_batch(e.h, C.size_t(len(cts)), u8(A), u8(B), u8(c)) })
+	if err != nil {
+		return nil, err
+	}
+	out := make([][]byte, len(cts))
+	for i := range out {
+		out[i] = c[32*i : 32*i+32]
+	}
+	return out, nil
+}
+
+// rq is the per-key factor R*(N/Key) mod N of the proof response (gadgets.go:44-47), n_len bytes.
+func (e *Engine) rq(sk *SecretKey) ([]byte, int) {
+	k := new(big.Int).Div(e.pk.N, sk.Key)
+	k.Mul(k, sk.R).Mod(k, e.pk.N)
+	nl := (e.pk.N.BitLen() + 7) / 8
+	return leftPad(k.Bytes(), nl), nl
+}
+
+// proofScalars reduces v, z, nonce1 modulo N and packs each as rows of n_len bytes.
+func (e *Engine) proofScalars(vs ...[]*big.Int) ([][]byte, int) {
+	nl := (e.pk.N.BitLen() + 7) / 8
+	out := make([][]byte, len(vs))
+	for k, v := range vs {
+		b := make([]byte, 0, nl*len(v))
+		for _, x := range v {
+			b = append(b, leftPad(new(big.Int).Mod(x, e.pk.N).Bytes(), nl)...)
+		}
+		out[k] = b
+	}
+	return out, nl
+}
+
+// NewProofOfPlaintextKnowledgeBatch is pk.NewProofOfPlaintextKnowledge (gadgets.go:32-54) over arrays in one call:
+// both encryptions, the hash and the response run on the device (bgn_prove_plaintext_knowledge_batch).  nonce1 is the
+// caller's randomness (gadgets.go:33), one per proof.
+func (e *Engine) NewProofOfPlaintextKnowledgeBatch(sk *SecretKey, v, z, nonce1 []*big.Int) ([]*ProofOfPlaintextKnowledge, error) {
+	if len(v) != len(z) || len(v) != len(nonce1) {
+		return nil, errors.New("bgn_amd: NewProofOfPlaintextKnowledgeBatch takes one z and one nonce per plaintext")
+	}
+	if len(v) == 0 {
+		return nil, nil
+	}
+	sc, nl := e.proofScalars(v, z, nonce1)
+	k, _ := e.rq(sk)
+	ct, nn, dl := make([]byte, len(v)*2*e.L), make([]byte, len(v)*2*e.L), make([]byte, len(v)*nl)
+	err := locked(func() C.int {
+		return C.bgn_prove_plaintext_knowledge_batch(e.h, C.size_t(len(v)), u8(sc[0]), C.size_t(nl), u8(sc[1]), C.size_t(nl),
+			u8(sc[2]), C.size_t(nl), u8(k), C.size_t(nl), u8(ct), u8(nn), u8(dl))
+	})
+	if err != nil {
+		return nil, err
+	}
+	cs, ns := e.unpack(ct, false), e.unpack(nn, false)
+	out := make([]*ProofOfPlaintextKnowledge, len(v))
+	for i := range out {
+		out[i] = &ProofOfPlaintextKnowledge{cs[i], ns[i], new(big.Int).SetBytes(dl[i*nl : (i+1)*nl])}
+	}
+	return out, nil
+}
+
+// VerifyPlaintextKnowledgeBatch is pk.CheckProofOfPlaintextKnoewledge (gadgets.go:65-77) over arrays with hash()
+// (gadgets.go:80-96) computed on the device (bgn_verify_plaintext_knowledge_batch).
+func (e *Engine) VerifyPlaintextKnowledgeBatch(cts []*Ciphertext, proofs []*ProofOfPlaintextKnowledge) ([]bool, error) {
+	if len(cts) != len(proofs) {
+		return nil, errors.New("bgn_amd: VerifyPlaintextKnowledgeBatch takes one proof per ciphertext")
+	}
+	if len(cts) == 0 {
+		return nil, nil
+	}
+	A := e.pack(cts)
+	PC, N := make([]byte, 0, len(A)), make([]byte, 0, len(A))
+	dls := make([]*big.Int, len(proofs))
+	for i, pr := range proofs {
+		PC = append(PC, e.wire(pr.Ct)...)
+		N = append(N, e.wire(pr.Nonce)...)
+		dls[i] = pr.DL
+	}
+	dl, dw := scalars(dls)
+	ok := make([]uint8, len(cts))
+	err := locked(func() C.int {
+		return C.bgn_verify_plaintext_knowledge_batch(e.h, C.size_t(len(cts)), u8(A), u8(PC), u8(N), u8(dl), C.size_t(dw), u8(ok))
 	})
 	if err != nil {
 		return nil, err
@@ -863,6 +963,112 @@ func (e *Engine) ValidateBatch(cts []*Ciphertext, l2 bool) ([]bool, error) {
 	A := e.pack(cts)
 	ok := make([]uint8, len(cts))
 	err := locked(func() C.int { return C.bgn_validate_batch(e.h, C.size_t(len(cts)), levelOf(l2), u8(A), u8(ok)) })
+	if err != nil {
+		return nil, err
+	}
+	return bools(ok), nil
+}
+
+// ChallengeBatchDev is ChallengeBatch on device arrays (bgn_challenge_batch_dev): Count x 32 digest bytes, left on
+// the device.
+func (e *Engine) ChallengeBatchDev(cts, nonces *DeviceArray) (*DeviceArray, error) {
+	if cts.Count != nonces.Count || cts.L2 || nonces.L2 {
+		return nil, errors.New("bgn_amd: ChallengeBatchDev takes two level-1 arrays of one count")
+	}
+	out, err := e.NewDeviceArray(cts.Count, 32, false)
+	if err != nil {
+		return nil, err
+	}
+	err = locked(func() C.int { return C.bgn_challenge_batch_dev(e.h, C.size_t(cts.Count), cts.u8(), nonces.u8(), out.u8(), nil) })
+	if err != nil {
+		out.Free()
+		return nil, err
+	}
+	return out, nil
+}
+
+// DeviceProofs is a batch of proofs of plaintext knowledge resident on the device: Ct and Nonce as wire elements, DL
+// as rows of n_len big-endian bytes.
+type DeviceProofs struct {
+	Ct, Nonce, DL *DeviceArray
+}
+
+// Free gives the three arrays back.
+func (p *DeviceProofs) Free() {
+	if p != nil {
+		p.Ct.Free()
+		p.Nonce.Free()
+		p.DL.Free()
+	}
+}
+
+// NewProofOfPlaintextKnowledgeBatchDev is NewProofOfPlaintextKnowledgeBatch with the proofs left on the device
+// (bgn_prove_plaintext_knowledge_batch_dev).
+func (e *Engine) NewProofOfPlaintextKnowledgeBatchDev(sk *SecretKey, v, z, nonce1 []*big.Int) (*DeviceProofs, error) {
+	if len(v) == 0 || len(v) != len(z) || len(v) != len(nonce1) {
+		return nil, errors.New("bgn_amd: NewProofOfPlaintextKnowledgeBatchDev takes one z and one nonce per plaintext")
+	}
+	sc, nl := e.proofScalars(v, z, nonce1)
+	k, _ := e.rq(sk)
+	in := make([]*DeviceArray, 0, 7)
+	free := func() {
+		for _, d := range in {
+			d.Free()
+		}
+	}
+	for i, b := range [][]byte{sc[0], sc[1], sc[2], k} {
+		count := len(v)
+		if i == 3 {
+			count = 1
+		}
+		d, err := e.uploadScalars(b, count, nl)
+		if err != nil {
+			free()
+			return nil, err
+		}
+		in = append(in, d)
+	}
+	for _, w := range []int{2 * e.L, 2 * e.L, nl} {
+		d, err := e.NewDeviceArray(len(v), w, false)
+		if err != nil {
+			free()
+			return nil, err
+		}
+		in = append(in, d)
+	}
+	err := locked(func() C.int {
+		return C.bgn_prove_plaintext_knowledge_batch_dev(e.h, C.size_t(len(v)), in[0].u8(), C.size_t(nl), in[1].u8(), C.size_t(nl),
+			in[2].u8(), C.size_t(nl), in[3].u8(), C.size_t(nl), in[4].u8(), in[5].u8(), in[6].u8(), nil)
+	})
+	if err != nil {
+		free()
+		return nil, err
+	}
+	out := &DeviceProofs{in[4], in[5], in[6]}
+	in = in[:4]
+	free()
+	return out, nil
+}
+
+// VerifyPlaintextKnowledgeBatchDev is VerifyPlaintextKnowledgeBatch on device-resident ciphertexts and proofs
+// (bgn_verify_plaintext_knowledge_batch_dev): only the verdicts are downloaded.
+func (e *Engine) VerifyPlaintextKnowledgeBatchDev(cts *DeviceArray, proofs *DeviceProofs) ([]bool, error) {
+	if cts.Count != proofs.Ct.Count || cts.L2 {
+		return nil, errors.New("bgn_amd: VerifyPlaintextKnowledgeBatchDev takes one proof per level-1 ciphertext")
+	}
+	okd, err := e.NewDeviceArray(cts.Count, 1, false)
+	if err != nil {
+		return nil, err
+	}
+	defer okd.Free()
+	err = locked(func() C.int {
+		return C.bgn_verify_plaintext_knowledge_batch_dev(e.h, C.size_t(cts.Count), cts.u8(), proofs.Ct.u8(), proofs.Nonce.u8(),
+			proofs.DL.u8(), C.size_t(proofs.DL.Width), okd.u8(), nil)
+	})
+	if err != nil {
+		return nil, err
+	}
+	ok, err := okd.DownloadBytes()
 	if err != nil {
 		return nil, err
 	}

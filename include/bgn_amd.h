@@ -263,14 +263,46 @@ int bgn_validate_batch(bgn_ctx* ctx, size_t count, int level, const uint8_t* in,
 int bgn_check_decryption_proof_batch(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* v_be, size_t v_len,
                                      const uint8_t* r_be, size_t r_len, uint8_t* ok);
 
-/* ok[i] = 1 iff ct[i]^c[i] * nonce[i] == P^dl[i], with c[i] the caller-computed challenge
- * sha256(proof.Ct.C.Bytes() || proof.Nonce.C.Bytes()) as a big-endian integer (hash(), gadgets.go:80-96,
- * stays on the host) and dl[i] = proof.DL.  Note the reference hashes the proof's own Ct but raises the
+/* ok[i] = 1 iff ct[i]^c[i] * nonce[i] == P^dl[i], with c[i] a challenge the CALLER computed:
+ * sha256(proof.Ct.C.Bytes() || proof.Nonce.C.Bytes()) as a big-endian integer (hash(), gadgets.go:80-96) and
+ * dl[i] = proof.DL.  Note the reference hashes the proof's own Ct but raises the
  * ciphertext under test to the challenge (gadgets.go:67-70): pass that one as ct.
+ * bgn_verify_plaintext_knowledge_batch below is this check with the challenge computed on the device; this form
+ * stays for callers that bring their own challenges.
  * Replaces CheckProofOfPlaintextKnoewledge (gadgets.go:65-77). */
 int bgn_check_plaintext_knowledge_batch(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* nonce,
                                         const uint8_t* c_be, size_t c_len, const uint8_t* dl_be, size_t dl_len,
                                         uint8_t* ok);
+
+/* Proofs of plaintext knowledge as batch calls, the hash included (gadgets.go:32-96).  None of the three joins the
+ * combiner of concurrent small calls: each stages its arrays by itself.
+ *
+ * c[i] = sha256(ct[i] || nonce[i]), 32 bytes each — the digest bytes, which the reference reads as a big-endian
+ * integer (c_be with c_len = 32 above).  Either array may start at any byte address.
+ * 2^20 device-resident pairs of a 1024-bit key: 1.5 ms (profiles/r08_proof_rates.csv).
+ * Replaces hash() (gadgets.go:80-96). */
+int bgn_challenge_batch(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* nonce, uint8_t* c_out);
+
+/* ct[i] = P^v[i] Q^z[i]; nonce[i] = P^nonce1[i]; dl[i] = (nonce1[i] + c[i] * (v[i] + rq * z[i])) mod n with
+ * c[i] = sha256(ct[i] || nonce[i]): count * n_len bytes, n_len = bytes of n, each the canonical residue in [0, n).
+ * rq = R * (n / q1) mod n (SecretKey.R, SecretKey.Key) is the caller's: it is not kept.  v, z, nonce1, rq: unsigned
+ * big-endian, at most n_len bytes each; any value that fits is taken, values >= n included.  The arithmetic modulo n
+ * has no branch and no address that depends on v, z, nonce1 or rq.
+ * 2^20 proofs of a 1024-bit key, device-resident: 178 ms, 5.9e6 /s (profiles/r08_proof_rates.csv).
+ * Replaces NewProofOfPlaintextKnowledge (gadgets.go:32-54); drawing nonce1 (gadgets.go:33) stays with the caller,
+ * like all randomness at this boundary. */
+int bgn_prove_plaintext_knowledge_batch(bgn_ctx* ctx, size_t count, const uint8_t* v_be, size_t v_len,
+                                        const uint8_t* z_be, size_t z_len, const uint8_t* nonce1_be, size_t nonce1_len,
+                                        const uint8_t* rq_be, size_t rq_len, uint8_t* ct_out, uint8_t* nonce_out,
+                                        uint8_t* dl_out);
+
+/* ok[i] = 1 iff ct[i]^c * nonce[i] == P^dl[i] with c = sha256(proof_ct[i] || nonce[i]) computed on the device.
+ * proof_ct is the proof's own Ct, ct the ciphertext under test (the reference hashes the one and raises the other,
+ * gadgets.go:67-70).  2^20 device-resident proofs of a 1024-bit key: 496 ms, against 1368 ms with the arrays
+ * downloaded, hashed on the host and checked by bgn_check_plaintext_knowledge_batch_dev (profiles/r08_proof_rates.csv).
+ * Replaces CheckProofOfPlaintextKnoewledge (gadgets.go:65-77) without a host hash. */
+int bgn_verify_plaintext_knowledge_batch(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* proof_ct,
+                                         const uint8_t* nonce, const uint8_t* dl_be, size_t dl_len, uint8_t* ok);
 
 /* ---- batch operations, device buffers (same semantics; asynchronous) --------
  * Aliasing: for Add / Sub / Neg / MultConst the result array may BE an operand array (out == a or out == b, the
@@ -299,12 +331,25 @@ int bgn_poly_eval_batch_dev(bgn_ctx* ctx, size_t npoly, size_t d, int level, con
                             uint8_t* out, void* stream);
 
 int bgn_validate_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* in, uint8_t* ok, void* stream);
-/* The two proof checks synchronise the stream before returning (they own scratch buffers). */
+/* The proof checks, Prove and Verify synchronise the stream before returning (they own scratch buffers);
+ * bgn_check_plaintext_knowledge_batch_dev takes challenges the caller computed, bgn_verify_plaintext_knowledge_batch_dev
+ * computes them from the device-resident proof. */
 int bgn_check_decryption_proof_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* v_be,
                                          size_t v_len, const uint8_t* r_be, size_t r_len, uint8_t* ok, void* stream);
 int bgn_check_plaintext_knowledge_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* nonce,
                                             const uint8_t* c_be, size_t c_len, const uint8_t* dl_be, size_t dl_len,
                                             uint8_t* ok, void* stream);
+
+/* The challenge alone is asynchronous (one kernel, no scratch).  rq_be of Prove is a device pointer like the others. */
+int bgn_challenge_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* nonce, uint8_t* c_out,
+                            void* stream);
+int bgn_prove_plaintext_knowledge_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* v_be, size_t v_len,
+                                            const uint8_t* z_be, size_t z_len, const uint8_t* nonce1_be,
+                                            size_t nonce1_len, const uint8_t* rq_be, size_t rq_len, uint8_t* ct_out,
+                                            uint8_t* nonce_out, uint8_t* dl_out, void* stream);
+int bgn_verify_plaintext_knowledge_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* proof_ct,
+                                             const uint8_t* nonce, const uint8_t* dl_be, size_t dl_len, uint8_t* ok,
+                                             void* stream);
 
 /* bgn_poly_mult_batch_dev builds per-coefficient line tables in an allocation of up to a sixth of the device's
  * memory, kept by the context between calls and given back when another per-key table is built (BGN_POLY_TABLES=0
@@ -415,7 +460,7 @@ double bgn_last_aux_kernel_ms(bgn_ctx* ctx);
 const char* bgn_last_aux_kernel_name(bgn_ctx* ctx);
 /* What the code object says about the kernel bgn_last_kernel_name names, when the engine knows its entry point
  * (the lane kernels: k_pairing<NL, 0|1>, k_g1_add_wire, k_gt_mul_wire, k_neg_wire, k_g1_add, k_gt_mul, k_g1_mul,
- * k_gt_pow, k_g1_fixed_chain): out[0] = vector registers per lane, out[1] = scratch
+ * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response): out[0] = vector registers per lane, out[1] = scratch
  * (private-segment) bytes per lane, out[2] = static LDS bytes per workgroup, out[3] = threads per workgroup the
  * kernel may be launched with.  A kernel that is meant to hold everything in registers and has started to spill
  * shows here before it shows on a clock.  Returns BGN_E_ARG for a kernel it has no entry point of. */

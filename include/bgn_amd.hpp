@@ -625,7 +625,61 @@ class PublicKey {
     return ok;
   }
 
-  // ---- gadgets.go:57-77 (verification; proof generation needs big-integer arithmetic and stays with the caller) ----
+  // ---- gadgets.go:32-96 with the hash on the device (bgn_challenge_batch, bgn_prove_plaintext_knowledge_batch,
+  // bgn_verify_plaintext_knowledge_batch) ----
+  // sha256(ct[i] || nonce[i]) as 32-byte big-endian scalars: hash(), gadgets.go:80-96
+  std::vector<Scalar> ChallengeBatch(const std::vector<Ciphertext>& cts, const std::vector<Ciphertext>& nonces) const {
+    std::vector<Scalar> out(cts.size());
+    if (cts.empty()) return out;
+    Bytes A = join(cts), B = join(nonces), c(cts.size() * 32);
+    check(bgn_challenge_batch(h_, cts.size(), A.data(), B.data(), c.data()), "bgn_challenge_batch");
+    for (size_t i = 0; i < out.size(); ++i) out[i].assign(c.begin() + i * 32, c.begin() + (i + 1) * 32);
+    return out;
+  }
+  // NewProofOfPlaintextKnowledge, gadgets.go:32-54, for a batch: v, z, nonce1 below n (the caller draws the nonces);
+  // rq = R * (n / q1) mod n, the big-integer arithmetic that stays with the caller, once per key.
+  std::vector<ProofOfPlaintextKnowledge> NewProofOfPlaintextKnowledgeBatch(const std::vector<Scalar>& v,
+                                                                           const std::vector<Scalar>& z,
+                                                                           const std::vector<Scalar>& nonce1,
+                                                                           const Scalar& rq) const {
+    std::vector<ProofOfPlaintextKnowledge> out(v.size());
+    if (v.empty()) return out;
+    size_t vl = 0, zl = 0, al = 0, kl = 0;
+    size_t nl = N.size();
+    while (nl > 1 && N[N.size() - nl] == 0) --nl;                          // bytes of n without leading zeros
+    Bytes vb = pack(v, vl), zb = pack(z, zl), ab = pack(nonce1, al), kb = pack({rq}, kl);
+    Bytes ct(v.size() * E_), nn(v.size() * E_), dl(v.size() * nl);
+    check(bgn_prove_plaintext_knowledge_batch(h_, v.size(), vb.data(), vl, zb.data(), zl, ab.data(), al, kb.data(), kl,
+                                              ct.data(), nn.data(), dl.data()),
+          "bgn_prove_plaintext_knowledge_batch");
+    const std::vector<Ciphertext> cs = split(ct, false), ns = split(nn, false);
+    for (size_t i = 0; i < out.size(); ++i) {
+      out[i].Ct = cs[i];
+      out[i].Nonce = ns[i];
+      out[i].DL.assign(dl.begin() + i * nl, dl.begin() + (i + 1) * nl);
+    }
+    return out;
+  }
+  // CheckProofOfPlaintextKnoewledge, gadgets.go:65-77, without a host hash
+  std::vector<uint8_t> VerifyProofOfPlaintextKnowledgeBatch(const std::vector<Ciphertext>& cts,
+                                                            const std::vector<ProofOfPlaintextKnowledge>& proofs) const {
+    std::vector<uint8_t> ok(cts.size());
+    if (cts.empty()) return ok;
+    std::vector<Scalar> dl;
+    std::vector<Ciphertext> own, nonces;
+    for (auto& pr : proofs) {
+      dl.push_back(pr.DL);
+      own.push_back(pr.Ct);
+      nonces.push_back(pr.Nonce);
+    }
+    size_t dll = 0;
+    Bytes A = join(cts), PC = join(own), Nn = join(nonces), db = pack(dl, dll);
+    check(bgn_verify_plaintext_knowledge_batch(h_, cts.size(), A.data(), PC.data(), Nn.data(), db.data(), dll, ok.data()),
+          "bgn_verify_plaintext_knowledge_batch");
+    return ok;
+  }
+
+  // ---- gadgets.go:57-77 (verification with challenges hashed here, on the host: sha256 below) ----
   std::vector<uint8_t> CheckDecryptionProofBatch(const std::vector<Ciphertext>& cts,
                                                  const std::vector<DecryptionProof>& proofs) const {
     std::vector<uint8_t> ok(cts.size());
