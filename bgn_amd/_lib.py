@@ -59,6 +59,10 @@ PROTOTYPES = {
     "bgn_prove_plaintext_knowledge_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, _sz, _u8p, _sz, _u8p, _sz, _u8p, _u8p, _u8p,
                                                           C.c_void_p]),
     "bgn_verify_plaintext_knowledge_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
+    "bgn_random_scalars_batch": (C.c_int, [_ctx, _sz, _u8p, C.c_uint64, C.c_uint64, _u8p]),
+    "bgn_encrypt_seeded_batch": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, C.c_uint64, C.c_uint64, _u8p]),
+    "bgn_random_scalars_batch_dev": (C.c_int, [_ctx, _sz, _u8p, C.c_uint64, C.c_uint64, _u8p, C.c_void_p]),
+    "bgn_encrypt_seeded_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, C.c_uint64, C.c_uint64, _u8p, C.c_void_p]),
     "bgn_encrypt_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_add_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_sub_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
@@ -81,6 +85,7 @@ PROTOTYPES = {
     "bgn_mctx_set_secret": (C.c_int, [_ctx, _u8p, _sz]),
     "bgn_mctx_setup_decryption": (C.c_int, [_ctx, C.c_uint64]),
     "bgn_mencrypt_batch": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, _sz, _u8p]),
+    "bgn_mencrypt_seeded_batch": (C.c_int, [_ctx, _sz, _u8p, _sz, _u8p, C.c_uint64, C.c_uint64, _u8p]),
     "bgn_madd_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p]),
     "bgn_msub_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p]),
     "bgn_mmult_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _sz, _u8p]),

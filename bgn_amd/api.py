@@ -396,6 +396,43 @@ class Engine:
                                                                  nonce.data_ptr(), dl.data_ptr(), dl_len, ok.data_ptr(),
                                                                  self._stream()), "bgn_verify_plaintext_knowledge_batch_dev")
 
+    # ---- blinding randomness expanded from a seed (include/bgn_amd.h "Randomness from a seed", expansion 1) -----------
+    @staticmethod
+    def _seed(seed: bytes) -> bytes:
+        seed = bytes(seed)
+        if len(seed) != 32:
+            raise ValueError("the seed is 32 bytes")
+        return seed
+
+    def random_scalars(self, count: int, seed: bytes, stream_id: int = 0, first_index: int = 0) -> np.ndarray:
+        """count x n_len bytes: row e = the scalar of (seed, stream_id, first_index + e) modulo n."""
+        out = np.zeros((count, self.n_len), dtype=np.uint8)
+        check(self._lib.bgn_random_scalars_batch(self._h, count, self._seed(seed), stream_id, first_index, _ptr(out)),
+              "bgn_random_scalars_batch")
+        return out
+
+    def encrypt_seeded(self, x: Sequence[int], seed: bytes, stream_id: int = 0, first_index: int = 0) -> np.ndarray:
+        """P^x[e] * Q^r[e] with r = random_scalars(len(x), seed, stream_id, first_index), expanded on the device."""
+        xs = _scalars(x)
+        out = self._out(len(xs))
+        check(self._lib.bgn_encrypt_seeded_batch(self._h, len(xs), _ptr(xs), xs.shape[1], self._seed(seed), stream_id,
+                                                 first_index, _ptr(out)), "bgn_encrypt_seeded_batch")
+        return out
+
+    def random_scalars_dev(self, out, count: int, seed: bytes, stream_id: int = 0, first_index: int = 0) -> None:
+        """Device-resident rows (any byte address): what the blinded `_dev` calls take as r with r_len = n_len."""
+        self._need("out", out, count * self.n_len)
+        check(self._lib.bgn_random_scalars_batch_dev(self._h, count, self._seed(seed), stream_id, first_index,
+                                                     out.data_ptr(), self._stream()), "bgn_random_scalars_batch_dev")
+
+    def encrypt_seeded_dev(self, x, x_len: int, out, count: int, seed: bytes, stream_id: int = 0, first_index: int = 0) -> None:
+        """Device-resident Encrypt from a seed: nothing but the 32 bytes comes from the host."""
+        self._need("x", x, count * x_len)
+        self._need("out", out, count * self.elem_bytes)
+        check(self._lib.bgn_encrypt_seeded_batch_dev(self._h, count, x.data_ptr(), x_len, self._seed(seed), stream_id,
+                                                     first_index, out.data_ptr(), self._stream()),
+              "bgn_encrypt_seeded_batch_dev")
+
     def field_ops(self, xy: BytesLike):
         """Diagnostics: (x*y || 1/x, x^2 || y^2) for elements x||y of plain residues (bgn_field_ops_batch)."""
         A = _as_u8(xy, self.elem_bytes)
@@ -560,6 +597,14 @@ class MultiEngine:
         out = self._out(len(xs))
         check(self._lib.bgn_mencrypt_batch(self._h, len(xs), _ptr(xs), xs.shape[1], _ptr(rs),
                                            rs.shape[1] if rs is not None else 0, _ptr(out)), "bgn_mencrypt_batch")
+        return out
+
+    def encrypt_seeded(self, x: Sequence[int], seed: bytes, stream_id: int = 0, first_index: int = 0) -> np.ndarray:
+        """Engine.encrypt_seeded over the devices: the same bytes whatever their number."""
+        xs = _scalars(x)
+        out = self._out(len(xs))
+        check(self._lib.bgn_mencrypt_seeded_batch(self._h, len(xs), _ptr(xs), xs.shape[1], Engine._seed(seed), stream_id,
+                                                  first_index, _ptr(out)), "bgn_mencrypt_seeded_batch")
         return out
 
     def _binop(self, fn, name, level, a, b):
@@ -758,6 +803,19 @@ class PublicKey:
         xs = [int(x) % self.N if int(x) < 0 else int(x) for x in xs]
         out = self.engine.encrypt(xs, rs)
         return [Ciphertext(bytes(row), False) for row in out]
+
+    def EncryptBatchSeeded(self, xs: Sequence[int], seed: Optional[bytes] = None, stream: int = 0, first_index: int = 0):
+        """Encrypt (bgn.go:334-337) for a batch with the randomness expanded on the device from a 32-byte seed
+        (drawn here when not given): returns (ciphertexts, seed).  The rows can be recomputed from the seed —
+        engine.random_scalars(len(xs), seed, stream, first_index) — e.g. for a DecryptionProof.  Never reuse a
+        (seed, stream, index) for another purpose: count `stream` up per call under one seed."""
+        if seed is None:
+            seed = secrets.token_bytes(32)
+        xs = [int(x) % self.N if int(x) < 0 else int(x) for x in xs]        # (as EncryptBatch)
+        if not xs:
+            return [], bytes(seed)
+        out = self.engine.encrypt_seeded(xs, seed, stream, first_index)
+        return [Ciphertext(bytes(row), False) for row in out], bytes(seed)
 
     def EncryptWithRandomness(self, x: int, r: int) -> Ciphertext:
         return self.EncryptBatch([x], [r])[0]

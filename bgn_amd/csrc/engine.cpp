@@ -164,6 +164,9 @@ struct bgn_ctx {
   // per-element multiple tables of the windowed variable-base scalar multiplication (grown on demand)
   uint8_t* mul_ws = nullptr;
   size_t mul_ws_bytes = 0;
+  // scalar rows of Encrypt from a seed (bgn_encrypt_seeded_batch_dev; grown on demand, wiped before it is given back)
+  uint8_t* rand_ws = nullptr;
+  size_t rand_ws_bytes = 0;
 
   // workspace arena (device)
   std::mutex mu;
@@ -476,6 +479,7 @@ void bgn_ctx_destroy(bgn_ctx* c) {
   if (c->d_params) (void)ctx_free(c, c->d_params);
   if (c->d_barrett) (void)ctx_free(c, c->d_barrett);
   if (c->d_params_n) (void)ctx_free(c, c->d_params_n);
+  if (c->rand_ws) (void)ctx_wipe_free(c, c->rand_ws);
   if (c->d_consts) (void)ctx_free(c, c->d_consts);
   if (c->d_a3) (void)ctx_free(c, c->d_a3);
   if (c->d_keypts) (void)ctx_free(c, c->d_keypts);
@@ -1807,16 +1811,11 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
   return BGN_OK;
 }
 
-int bgn_encrypt_batch_dev(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* r_be, size_t r_len,
-                          uint8_t* out, void* stream) {
-  if (!c || (count && (!x_be || !out))) return fail(BGN_E_ARG, "null argument");
-  if (!x_len || (r_be && !r_len)) return fail(BGN_E_ARG, "zero scalar length");
-  if (!count) return BGN_OK;
-  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
-  hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> lk(c->mu);
-  StreamOrder order(c, s);
-  HIP_TRY(hipSetDevice(c->device));
+namespace {
+// The Encrypt chain on stream s: P^x * Q^r (r_be may be null) from the window tables, or by the generic ladders for
+// over-long scalars.  c->mu held, the stream ordered (StreamOrder), the device set, the arguments checked.
+int encrypt_chain(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* r_be, size_t r_len, uint8_t* out,
+                  hipStream_t s) {
   const size_t st = round_up(count, 64);
   SoA2 G, H, O;
   uint32_t* prefix = nullptr;
@@ -1858,6 +1857,92 @@ int bgn_encrypt_batch_dev(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t 
   c->last_kernel = "k_g1_mul";
   HIP_TRY(hipGetLastError());
   return BGN_OK;
+}
+}  // namespace
+
+int bgn_encrypt_batch_dev(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* r_be, size_t r_len,
+                          uint8_t* out, void* stream) {
+  if (!c || (count && (!x_be || !out))) return fail(BGN_E_ARG, "null argument");
+  if (!x_len || (r_be && !r_len)) return fail(BGN_E_ARG, "zero scalar length");
+  if (!count) return BGN_OK;
+  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  return encrypt_chain(c, count, x_be, x_len, r_be, r_len, out, s);
+}
+
+// ---- blinding randomness expanded from a caller's seed (bgn.go:334-337, :567-574; randexp.hpp) ----------------------
+// Randomness stays an input: 32 bytes per call instead of n_len bytes per element.  k_random_scalars expands (seed,
+// stream_id, first_index + e) into row e by "expansion 1" of include/bgn_amd.h; the seed goes into the kernel's
+// arguments and nowhere else.  Encrypt from a seed is that kernel into a scalar array of the context, in front of the
+// Encrypt chain above, on one stream.
+namespace {
+int seeded_args(const void* ctx, size_t count, const uint8_t* seed32, uint64_t first_index, const void* out) {
+  if (!ctx || (count && (!seed32 || !out))) return fail(BGN_E_ARG, "null argument");
+  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  if (count && first_index > UINT64_MAX - (uint64_t)(count - 1)) return fail(BGN_E_ARG, "first_index + count exceeds 2^64");
+  return BGN_OK;
+}
+
+// c->mu held
+int random_launch(bgn_ctx* c, hipStream_t s, const uint8_t* seed32, uint64_t stream_id, uint64_t first_index, size_t count,
+                  uint8_t* out) {
+  if (c->n_len > (size_t)(LIMB_BITS * c->nl - 2) / 8)      // randexp.hpp RandShape<NL>::MAX_N_LEN (true of every key: n < p)
+    return fail(BGN_E_PARAM, "group order of %zu bytes exceeds what %d limbs serve", c->n_len, c->nl);
+  RandSeed k;
+  for (int m = 0; m < 8; ++m)
+    k.w[m] = (uint32_t)seed32[4 * m] << 24 | (uint32_t)seed32[4 * m + 1] << 16 | (uint32_t)seed32[4 * m + 2] << 8 | seed32[4 * m + 3];
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  c->kt->random_scalars(s, c->d_params_n, k, stream_id, first_index, count, c->n_len, out);
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->ev_valid = true;
+  c->last_kernel = "k_random_scalars";
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+}  // namespace
+
+int bgn_random_scalars_batch_dev(bgn_ctx* c, size_t count, const uint8_t* seed32, uint64_t stream_id, uint64_t first_index,
+                                 uint8_t* r_out, void* stream) {
+  if (int rc = seeded_args(c, count, seed32, first_index, r_out)) return rc;
+  if (!count) return BGN_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  std::lock_guard<std::mutex> lk(c->mu);
+  return random_launch(c, (hipStream_t)stream, seed32, stream_id, first_index, count, r_out);
+}
+
+int bgn_encrypt_seeded_batch_dev(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* seed32,
+                                 uint64_t stream_id, uint64_t first_index, uint8_t* out, void* stream) {
+  if (int rc = seeded_args(c, count, seed32, first_index, out)) return rc;
+  if (count && !x_be) return fail(BGN_E_ARG, "null argument");
+  if (!x_len) return fail(BGN_E_ARG, "zero scalar length");
+  if (!count) return BGN_OK;
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  // the scalar rows: an array the context keeps and grows (like chain_ws), ordered across streams with the workspace —
+  // the call stays asynchronous unless the array has to grow
+  const size_t need = count * c->n_len;
+  if (need > c->rand_ws_bytes) {
+    if (c->rand_ws) {
+      HIP_TRY(hipDeviceSynchronize());
+      HIP_TRY(ctx_wipe_free(c, c->rand_ws));
+      c->rand_ws = nullptr;
+      c->rand_ws_bytes = 0;
+    }
+    const size_t want = round_up(need + need / 8, 1 << 16);
+    if (ctx_malloc(c, (void**)&c->rand_ws, want) != hipSuccess) {
+      (void)hipGetLastError();
+      c->rand_ws = nullptr;
+      return fail(BGN_E_NOMEM, "scalar rows of %zu bytes: device memory or the context's memory budget exhausted", want);
+    }
+    c->rand_ws_bytes = want;
+  }
+  if (int rc = random_launch(c, s, seed32, stream_id, first_index, count, c->rand_ws)) return rc;
+  return encrypt_chain(c, count, x_be, x_len, c->rand_ws, c->n_len, out, s);      // bgn.go:344-350
 }
 
 // ==== host-buffer entry points ================================================================================
@@ -2289,6 +2374,30 @@ int bgn_encrypt_batch(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t x_le
   if (!count) return BGN_OK;
   return host_call(c, COMB_ENCRYPT, 1,
                    {{x_be, nullptr, x_len, count}, {r_be, nullptr, r_len, count}, {nullptr, out, 2 * (size_t)c->L, count}});
+}
+
+// The seeded forms bring their own device side (no CombineOp): a seed belongs to one call, so they are never merged with
+// concurrent calls, and the whole call is one launch sequence with the caller's first_index.
+int bgn_random_scalars_batch(bgn_ctx* c, size_t count, const uint8_t* seed32, uint64_t stream_id, uint64_t first_index,
+                             uint8_t* r_out) {
+  if (int rc = seeded_args(c, count, seed32, first_index, r_out)) return rc;
+  if (!count) return BGN_OK;
+  return host_call(c, 0, 0, {{nullptr, r_out, c->n_len, count}},
+                   [&](size_t n, uint8_t* const*, uint8_t* const* o, hipStream_t s) {
+                     return bgn_random_scalars_batch_dev(c, n, seed32, stream_id, first_index, o[0], s);
+                   });
+}
+
+int bgn_encrypt_seeded_batch(bgn_ctx* c, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* seed32,
+                             uint64_t stream_id, uint64_t first_index, uint8_t* out) {
+  if (int rc = seeded_args(c, count, seed32, first_index, out)) return rc;
+  if (count && !x_be) return fail(BGN_E_ARG, "null argument");
+  if (!x_len) return fail(BGN_E_ARG, "zero scalar length");
+  if (!count) return BGN_OK;
+  return host_call(c, 0, 0, {{x_be, nullptr, x_len, count}, {nullptr, out, 2 * (size_t)c->L, count}},
+                   [&](size_t n, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_encrypt_seeded_batch_dev(c, n, in[0], x_len, seed32, stream_id, first_index, o[0], s);
+                   });
 }
 
 int bgn_add_batch(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,

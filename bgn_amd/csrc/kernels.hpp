@@ -238,6 +238,11 @@ struct PokArgs {
   size_t count;
 };
 
+// The seed of bgn_random_scalars_batch as eight big-endian 32-bit words: a kernel argument, never device memory.
+struct RandSeed {
+  uint32_t w[8];
+};
+
 struct KernelTable {
   int nl;
   size_t params_bytes;   // sizeof(FpParams<NL>)
@@ -326,9 +331,13 @@ struct KernelTable {
   void (*challenge)(hipStream_t s, const uint8_t* a, const uint8_t* b, size_t len_each, size_t count, uint8_t* out);
   // proof responses modulo n; params_n = FpParams<NL> with n for the modulus (engine.cpp build_params(n))
   void (*pok_response)(hipStream_t s, const void* params_n, PokArgs a);
+  // out row e (n_len bytes, any byte address) = the scalar of (seed, stream_id, first_index + e) modulo n, expansion 1
+  // of include/bgn_amd.h (randexp.hpp); the seed travels in the kernel arguments
+  void (*random_scalars)(hipStream_t s, const void* params_n, RandSeed seed, uint64_t stream_id, uint64_t first_index,
+                         size_t count, size_t n_len, uint8_t* out);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
-  Entry entries[14];
+  Entry entries[15];
 };
 
 const KernelTable* kernel_table_nl3();

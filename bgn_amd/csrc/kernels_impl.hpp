@@ -10,6 +10,7 @@
 #include "barrett.hpp"
 #include "sha256.hpp"
 #include "proofs.hpp"
+#include "randexp.hpp"
 
 namespace bgn {
 
@@ -1257,6 +1258,27 @@ static void launch_pok_response(hipStream_t s, const void* params_n, PokArgs a) 
   hipLaunchKernelGGL(k_pok_response<NL_>, dim3(grid_for(a.count)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params_n, a);
 }
 
+// ---- blinding scalars from a seed (bgn.go:334-337, :567-574; randexp.hpp) --------------------------------------------
+// out row e = the scalar of (K, t, first + e), n_len big-endian bytes at any byte address: one scalar per lane.  The seed
+// is a kernel argument and goes from there into the message words; the scalars are secrets — every lane runs the same
+// instructions and writes row e, whatever the values.
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_random_scalars(const FpParams<NL>* __restrict__ N, RandSeed K, u64 t, u64 first, size_t count, int n_len,
+                 uint8_t* __restrict__ out) {
+  __shared__ LFp<NL> stage;
+  const size_t e = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  if (e >= count) return;
+  rand_scalar_bytes<NL>(out + e * (size_t)n_len, n_len, K.w, t, first + (u64)e, N, &stage);
+}
+
+static void launch_random_scalars(hipStream_t s, const void* params_n, RandSeed seed, uint64_t stream_id, uint64_t first_index,
+                                  size_t count, size_t n_len, uint8_t* out) {
+  if (!count || n_len > (size_t)RandShape<NL_>::MAX_N_LEN) return;      // (no key of this limb count has a longer order)
+  hipLaunchKernelGGL(k_random_scalars<NL_>, dim3(grid_for(count)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params_n, seed,
+                     (u64)stream_id, (u64)first_index, count, (int)n_len, out);
+}
+
 const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
   static const KernelTable t = {
       NL_,
@@ -1306,6 +1328,7 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
 #endif
       launch_challenge,
       launch_pok_response,
+      launch_random_scalars,
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1320,6 +1343,7 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
        {"k_g1_fixed_chain", (const void*)k_g1_fixed_chain<NL_>},
        {"k_challenge", (const void*)k_challenge<NL_>},
        {"k_pok_response", (const void*)k_pok_response<NL_>},
+       {"k_random_scalars", (const void*)k_random_scalars<NL_>},
        {nullptr, nullptr}},
   };
   return &t;

@@ -259,6 +259,20 @@ int bgn_mencrypt_batch(bgn_mctx* m, size_t count, const uint8_t* x_be, size_t x_
   });
 }
 
+// Encrypt from a seed: shard [lo, hi) expands the indices first_index + lo .. first_index + hi - 1, so the rows — and
+// the ciphertexts — do not depend on the number of devices.
+int bgn_mencrypt_seeded_batch(bgn_mctx* m, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* seed32,
+                              uint64_t stream_id, uint64_t first_index, uint8_t* out) {
+  if (!m || (count && (!x_be || !seed32 || !out))) return mfail(BGN_E_ARG, "null argument");
+  if (!x_len) return mfail(BGN_E_ARG, "zero scalar length");
+  if (count && first_index > UINT64_MAX - (uint64_t)(count - 1)) return mfail(BGN_E_ARG, "first_index + count exceeds 2^64");
+  const size_t eb = 2 * m->L;
+  return run_sharded(m, count, [&](int i, size_t lo, size_t hi) {
+    return bgn_encrypt_seeded_batch(m->ctx[i], hi - lo, x_be + lo * x_len, x_len, seed32, stream_id, first_index + lo,
+                                    out + lo * eb);
+  });
+}
+
 int bgn_madd_batch(bgn_mctx* m, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
                    size_t r_len, uint8_t* out) {
   if (!m || (count && (!a || !b || !out))) return mfail(BGN_E_ARG, "null argument");

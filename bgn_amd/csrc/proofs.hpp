@@ -23,28 +23,33 @@ namespace bgn {
 constexpr int POK_C_BYTES = 32;                                            // a sha256 digest
 constexpr int POK_C_LIMBS = (8 * POK_C_BYTES + LIMB_BITS - 1) / LIMB_BITS;  // 9 limbs of 29 bits
 
-// c*R mod n, lazy, for the 256-bit challenge c given as POK_C_LIMBS tight limbs.  c = sum_k piece_k * R^k with pieces of
-// NL limbs (R = 2^(LIMB_BITS*NL)): one piece from 9 limbs up, three at NL = 3; Horner over the pieces in Montgomery
-// form, where a product by r2 is a product by R.
-template <int NL>
-__device__ __forceinline__ void pok_challenge_to_mont(Fp<NL>& r, const Fp<POK_C_LIMBS>& c, const Fp<NL>& r2,
-                                                      const FpParams<NL>* __restrict__ N, LFp<NL>* stage) {
-  constexpr int NPIECE = (POK_C_LIMBS + NL - 1) / NL;
-  Fp<NL> acc;
+// w*R mod n, lazy, for an integer w of any length given as CL tight limbs: the 256-bit challenge (CL = POK_C_LIMBS) and
+// the over-long draw of randexp.hpp.  w = sum_k piece_k * R^k with pieces of NL limbs (R = 2^(LIMB_BITS*NL)): one piece
+// when CL <= NL, three for the challenge at NL = 3; Horner over the pieces in Montgomery form, where a product by r2 is
+// a product by R.  The bounds hold for any number of pieces: the accumulator is <4 going into a product and <2 out of it.
+// (The pieces are taken by template recursion, from the top one down, not by a loop: with products of 36 limbs in its
+// body a loop is not unrolled, and a run-time piece index would send c to scratch memory.)
+template <int NL, int CL, int K>
+__device__ __forceinline__ void wide_horner(Fp<NL>& acc, const Fp<CL>& c, const Fp<NL>& r2,
+                                            const FpParams<NL>* __restrict__ N, LFp<NL>* stage) {
+  constexpr int NPIECE = (CL + NL - 1) / NL;
+  Fp<NL> piece, t;
 #pragma unroll
-  for (int k = NPIECE - 1; k >= 0; --k) {
-    Fp<NL> piece, t;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) piece.v[j] = (k * NL + j < POK_C_LIMBS) ? c.v[k * NL + j < POK_C_LIMBS ? k * NL + j : 0] : 0u;
-    fp_mulv(t, piece, r2, N, stage);               // piece < R, r2 < 1: piece*R <2
-    if (k == NPIECE - 1) {
-      acc = t;                                     // <2
-    } else {
-      fp_mulv(acc, acc, r2, N, stage);             // <4 * <1: acc*R <2
-      fp_add(acc, acc, t);                         // <4
-    }
+  for (int j = 0; j < NL; ++j) piece.v[j] = (K * NL + j < CL) ? c.v[K * NL + j < CL ? K * NL + j : 0] : 0u;
+  fp_mulv(t, piece, r2, N, stage);                 // piece < R, r2 < 1: piece*R <2
+  if constexpr (K == NPIECE - 1) {
+    acc = t;                                       // <2
+  } else {
+    fp_mulv(acc, acc, r2, N, stage);               // <4 * <1: acc*R <2
+    fp_add(acc, acc, t);                           // <4
   }
-  r = acc;                                         // <4 (<2 with one piece)
+  if constexpr (K > 0) wide_horner<NL, CL, K - 1>(acc, c, r2, N, stage);
+}
+
+template <int NL, int CL>
+__device__ __forceinline__ void wide_to_mont(Fp<NL>& r, const Fp<CL>& c, const Fp<NL>& r2,
+                                             const FpParams<NL>* __restrict__ N, LFp<NL>* stage) {
+  wide_horner<NL, CL, (CL + NL - 1) / NL - 1>(r, c, r2, N, stage);      // <4 (<2 with one piece)
 }
 
 // dl = (nonce1 + c*(v + K*z)) mod n, canonical in [0, n).  v, z, a (= nonce1), K: tight limbs of any value below R.
@@ -54,7 +59,7 @@ __device__ __forceinline__ void pok_response(Fp<NL>& dl, const Fp<NL>& v, const 
                                              const FpParams<NL>* __restrict__ N, LFp<NL>* stage) {
   Fp<NL> r2, cm, t, u;
   fp_set(r2, N->r2);                               // <1
-  pok_challenge_to_mont<NL>(cm, c, r2, N, stage);  // c*R <4
+  wide_to_mont<NL, POK_C_LIMBS>(cm, c, r2, N, stage);  // c*R <4
   fp_mulv(t, K, r2, N, stage);                     // K < R, r2 <1: K*R <2
   fp_mulv(u, z, r2, N, stage);                     // z*R <2
   fp_mulv(t, t, u, N, stage);                      // <2 * <2: K*z*R <2

@@ -87,6 +87,17 @@ __device__ __forceinline__ u32 sha_msg_word(const uint8_t* a, const uint8_t* b, 
   BGN_SHA_RND(c, d, e, f, g, h, a, b, (t) + 6, k6);        \
   BGN_SHA_RND(b, c, d, e, f, g, h, a, (t) + 7, k7)
 
+// the 64 rounds of one compression over w[16] and a..h (FIPS 180-4 section 4.2.2 constants)
+#define BGN_SHA_ROUNDS64()                                                                                             \
+  BGN_SHA_RND8(0, 0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u); \
+  BGN_SHA_RND8(8, 0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u); \
+  BGN_SHA_RND8(16, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau); \
+  BGN_SHA_RND8(24, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u); \
+  BGN_SHA_RND8(32, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u); \
+  BGN_SHA_RND8(40, 0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u); \
+  BGN_SHA_RND8(48, 0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u); \
+  BGN_SHA_RND8(56, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u)
+
 // out[0..8) = the state words of sha256(pa[0..len_each) || pb[0..len_each)): the digest is their big-endian bytes in
 // order.  Reads only bytes of the two arrays (through the aligned dwords that hold them).
 __device__ __forceinline__ void sha256_wire(const uint8_t* pa, const uint8_t* pb, size_t len_each, u32 out[8]) {
@@ -100,14 +111,7 @@ __device__ __forceinline__ void sha256_wire(const uint8_t* pa, const uint8_t* pb
 #pragma unroll
     for (int i = 0; i < 16; ++i) w[i] = sha_msg_word(pa, pb, len_each, padded, 16 * blk + (size_t)i);
     u32 a = h0, b = h1, c = h2, d = h3, e = h4, f = h5, g = h6, h = h7;
-    BGN_SHA_RND8(0, 0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u);
-    BGN_SHA_RND8(8, 0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u);
-    BGN_SHA_RND8(16, 0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau);
-    BGN_SHA_RND8(24, 0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u);
-    BGN_SHA_RND8(32, 0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u);
-    BGN_SHA_RND8(40, 0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u);
-    BGN_SHA_RND8(48, 0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u);
-    BGN_SHA_RND8(56, 0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u);
+    BGN_SHA_ROUNDS64();
     h0 += a; h1 += b; h2 += c; h3 += d; h4 += e; h5 += f; h6 += g; h7 += h;
   }
   out[0] = h0; out[1] = h1; out[2] = h2; out[3] = h3; out[4] = h4; out[5] = h5; out[6] = h6; out[7] = h7;

@@ -31,6 +31,7 @@ package bgn
 import "C"
 
 import (
+	"crypto/rand"
 	"encoding/binary"
 	"errors"
 	"math/big"
@@ -768,6 +769,102 @@ func (e *Engine) EncryptBatchDev(x []*big.Int, r []*big.Int) (*DeviceArray, erro
 	return out, nil
 }
 
+// ---- randomness expanded on the device from a 32-byte seed (include/bgn_amd.h "Randomness from a seed") -----------------
+// The caller draws the seed (crypto/rand) and never uses the same (seed, streamID, index) twice: count streamID up per
+// call under one seed.  Element e of a call uses the index firstIndex + e.
+
+// NewSeed draws a seed from crypto/rand.
+func NewSeed() (*[32]byte, error) {
+	var s [32]byte
+	if _, err := rand.Read(s[:]); err != nil {
+		return nil, err
+	}
+	return &s, nil
+}
+
+// RandomScalars returns the count scalars of (seed, streamID, firstIndex ..) modulo N: what newCryptoRandom(N)
+// (bgn.go:567-574) is to one element (bgn_random_scalars_batch).
+func (e *Engine) RandomScalars(count int, seed *[32]byte, streamID, firstIndex uint64) ([]*big.Int, error) {
+	w := len(e.pk.N.Bytes())
+	out := make([]byte, count*w)
+	err := locked(func() C.int {
+		return C.bgn_random_scalars_batch(e.h, C.size_t(count), (*C.uint8_t)(unsafe.Pointer(&seed[0])), C.uint64_t(streamID),
+			C.uint64_t(firstIndex), u8(out))
+	})
+	if err != nil {
+		return nil, err
+	}
+	r := make([]*big.Int, count)
+	for i := range r {
+		r[i] = new(big.Int).SetBytes(out[i*w : (i+1)*w])
+	}
+	return r, nil
+}
+
+// EncryptBatchSeeded is pk.Encrypt with Deterministic == false (bgn.go:334-337) over an array: EncryptBatch(x, r) with
+// r = RandomScalars(len(x), seed, streamID, firstIndex), the rows never leaving the device (bgn_encrypt_seeded_batch).
+func (e *Engine) EncryptBatchSeeded(x []*big.Int, seed *[32]byte, streamID, firstIndex uint64) ([]*Ciphertext, error) {
+	xs := make([]*big.Int, len(x))
+	for i, v := range x {
+		xs[i] = new(big.Int).Mod(v, e.pk.N)
+	}
+	xb, xw := scalars(xs)
+	out := make([]byte, len(x)*2*e.L)
+	err := locked(func() C.int {
+		return C.bgn_encrypt_seeded_batch(e.h, C.size_t(len(x)), u8(xb), C.size_t(xw), (*C.uint8_t)(unsafe.Pointer(&seed[0])),
+			C.uint64_t(streamID), C.uint64_t(firstIndex), u8(out))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return e.unpack(out, false), nil
+}
+
+// RandomScalarsDev leaves the rows on the device (width: the bytes of N): the r of the blinded *Dev calls
+// (bgn_random_scalars_batch_dev).
+func (e *Engine) RandomScalarsDev(count int, seed *[32]byte, streamID, firstIndex uint64) (*DeviceArray, error) {
+	out, err := e.NewDeviceArray(count, len(e.pk.N.Bytes()), false)
+	if err != nil {
+		return nil, err
+	}
+	err = locked(func() C.int {
+		return C.bgn_random_scalars_batch_dev(e.h, C.size_t(count), (*C.uint8_t)(unsafe.Pointer(&seed[0])), C.uint64_t(streamID),
+			C.uint64_t(firstIndex), out.u8(), nil)
+	})
+	if err != nil {
+		out.Free()
+		return nil, err
+	}
+	return out, nil
+}
+
+// EncryptBatchSeededDev is EncryptBatchSeeded with the ciphertexts left on the device (bgn_encrypt_seeded_batch_dev).
+func (e *Engine) EncryptBatchSeededDev(x []*big.Int, seed *[32]byte, streamID, firstIndex uint64) (*DeviceArray, error) {
+	xs := make([]*big.Int, len(x))
+	for i, v := range x {
+		xs[i] = new(big.Int).Mod(v, e.pk.N)
+	}
+	xb, xw := scalars(xs)
+	dx, err := e.uploadScalars(xb, len(x), xw)
+	if err != nil {
+		return nil, err
+	}
+	defer dx.Free()
+	out, err := e.likeOut(len(x), false)
+	if err != nil {
+		return nil, err
+	}
+	err = locked(func() C.int {
+		return C.bgn_encrypt_seeded_batch_dev(e.h, C.size_t(len(x)), dx.u8(), C.size_t(xw), (*C.uint8_t)(unsafe.Pointer(&seed[0])),
+			C.uint64_t(streamID), C.uint64_t(firstIndex), out.u8(), nil)
+	})
+	if err != nil {
+		out.Free()
+		return nil, err
+	}
+	return out, nil
+}
+
 func (e *Engine) addSubDev(a, b *DeviceArray, r []*big.Int, sub bool) (*DeviceArray, error) {
 	if a.Count != b.Count || a.L2 != b.L2 {
 		return nil, errors.New("bgn_amd: operand arrays differ in count or level")
@@ -1253,6 +1350,25 @@ func (m *MultiEngine) MultBatch(a, b []*Ciphertext, r []*big.Int) ([]*Ciphertext
 		return nil, err
 	}
 	return m.e0.unpack(out, true), nil
+}
+
+// EncryptBatchSeeded: Engine.EncryptBatchSeeded sharded over the GPUs; shard [lo, hi) expands the indices
+// firstIndex + lo .., so the ciphertexts do not depend on the number of devices (bgn_mencrypt_seeded_batch).
+func (m *MultiEngine) EncryptBatchSeeded(x []*big.Int, seed *[32]byte, streamID, firstIndex uint64) ([]*Ciphertext, error) {
+	xs := make([]*big.Int, len(x))
+	for i, v := range x {
+		xs[i] = new(big.Int).Mod(v, m.e0.pk.N)
+	}
+	xb, xw := scalars(xs)
+	out := make([]byte, len(x)*2*m.e0.L)
+	err := locked(func() C.int {
+		return C.bgn_mencrypt_seeded_batch(m.h, C.size_t(len(x)), u8(xb), C.size_t(xw), (*C.uint8_t)(unsafe.Pointer(&seed[0])),
+			C.uint64_t(streamID), C.uint64_t(firstIndex), u8(out))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return m.e0.unpack(out, false), nil
 }
 
 // DecryptBatch: sk.Decrypt over len(cts) ciphertexts, sharded over the GPUs (bgn.go:205-250).

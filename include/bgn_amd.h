@@ -18,7 +18,10 @@
  *   - Scalars (plaintexts, randomness, constants) are unsigned big-endian
  *     integers of a caller-chosen fixed byte length per call.
  *   - Randomness is always an input (like EncryptWithRandomness, bgn.go:340);
- *     the engine never draws random numbers.
+ *     the engine never draws random numbers.  It takes rows of scalars the
+ *     caller drew, or expands a 32-byte seed the caller drew into such rows by
+ *     the fixed rule specified under "Randomness from a seed" below; either way
+ *     a result is a function of the arguments and can be checked byte for byte.
  *   - `level` is 1 for G1 ciphertexts (Ciphertext.L2 == false) and 2 for GT.
  *   - Functions return 0 on success or a negative BGN_E_* code; no exception or
  *     abort crosses the ABI.  bgn_last_error() returns a thread-local message.
@@ -182,6 +185,38 @@ int bgn_ctx_setup_decryption(bgn_ctx* ctx, uint64_t msg_space);
 int bgn_encrypt_batch(bgn_ctx* ctx, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* r_be,
                       size_t r_len, uint8_t* out);
 
+/* ---- Randomness from a seed: expansion 1 (normative) --------------------------
+ * Inputs: a seed K of 32 bytes, a stream id t (u64), an element index i (u64); n is the group order, n_len its bytes.
+ *
+ *     B_j = SHA-256( K || be64(t) || be64(i) || be32(j) )      j = 0, 1, ... (u32); a message of 52 bytes
+ *     W   = (B_0 || B_1 || ...) truncated to n_len + 16 bytes, read as a big-endian integer
+ *     r   = W mod n, written as n_len big-endian bytes
+ *
+ * W has 128 bits more than n, so r is within 2^-128 of uniform on [0, n).  Every message has the same length: none is
+ * a prefix of another, length extension does not apply and no HMAC wrapping is needed.  Element e of a call uses
+ * i = first_index + e; a call with first_index + count above 2^64 is BGN_E_ARG.  The rule is versioned: a change of it
+ * would be "expansion 2" under new entry points, never a change of these.
+ *
+ * What the caller owes: K from the operating system's generator (getrandom, crypto/rand, secrets.token_bytes), kept as
+ * secret as the scalars themselves; and never the same (K, t, i) for two different uses — two ciphertexts blinded with
+ * the same r are linked.  Keeping t as a per-seed call counter (and first_index = 0, or the offset of a shard) does it.
+ * The engine keeps no generator state: K, t and first_index are arguments of every call, and K goes from the
+ * argument into the kernel's arguments without being written to device memory.  The expansion has no branch and no
+ * address that depends on K or on a scalar.
+ *
+ * r_out[e] = r(K = seed32, t = stream_id, i = first_index + e): count * n_len bytes, n_len = bytes of n.  The rows are
+ * what bgn_encrypt_batch and the blinded Add / Mult / MultConst take as r (r_len = n_len).
+ * Replaces newCryptoRandom(N) (bgn.go:567-574) for a batch; drawing the seed stays with the caller. */
+int bgn_random_scalars_batch(bgn_ctx* ctx, size_t count, const uint8_t* seed32, uint64_t stream_id, uint64_t first_index,
+                             uint8_t* r_out);
+
+/* out[e] = P^x[e] * Q^r[e] with r[e] as above: byte for byte bgn_encrypt_batch(x, r) with the rows
+ * bgn_random_scalars_batch returns for the same (seed32, stream_id, first_index).  The rows never leave the device.
+ * Neither call joins the combiner of concurrent small calls (a seed belongs to one call).
+ * Replaces Encrypt with Deterministic == false (bgn.go:334-337). */
+int bgn_encrypt_seeded_batch(bgn_ctx* ctx, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* seed32,
+                             uint64_t stream_id, uint64_t first_index, uint8_t* out);
+
 /* out[i] = a[i] + b[i] (level 1: G1 point addition; level 2: F_p^2 product),
  * followed by blinding with Q^r[i] resp. e(Q,Q)^r[i] when r != NULL.
  * With r == NULL a call is ONE kernel launch from wire bytes to wire bytes on either level (and so are Sub and
@@ -340,6 +375,17 @@ int bgn_check_plaintext_knowledge_batch_dev(bgn_ctx* ctx, size_t count, const ui
                                             const uint8_t* c_be, size_t c_len, const uint8_t* dl_be, size_t dl_len,
                                             uint8_t* ok, void* stream);
 
+/* Randomness from a seed (expansion 1 above).  seed32 is a HOST pointer to 32 bytes, read before the call returns;
+ * r_out / x_be / out are device pointers, rows at any byte address.  Both calls are asynchronous on `stream`:
+ * bgn_random_scalars_batch_dev is one kernel without scratch; bgn_encrypt_seeded_batch_dev expands into an array of
+ * scalar rows the context keeps between calls (count * n_len bytes, ordered across streams like the workspace) and
+ * synchronises the device only when that array has to grow — warm the context up with the largest batch first, as
+ * for the workspace.  Pass the rows of bgn_random_scalars_batch_dev as r to the blinded Add / Mult / MultConst. */
+int bgn_random_scalars_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* seed32, uint64_t stream_id,
+                                 uint64_t first_index, uint8_t* r_out, void* stream);
+int bgn_encrypt_seeded_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* seed32,
+                                 uint64_t stream_id, uint64_t first_index, uint8_t* out, void* stream);
+
 /* The challenge alone is asynchronous (one kernel, no scratch).  rq_be of Prove is a device pointer like the others. */
 int bgn_challenge_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* ct, const uint8_t* nonce, uint8_t* c_out,
                             void* stream);
@@ -387,6 +433,10 @@ int bgn_mctx_set_option(bgn_mctx* m, const char* name, int64_t value);
  * Mult :294-314, makeL2 :316-321, MultConst :253-291, Decrypt :205-250, MultPoly poly.go:123-156). */
 int bgn_mencrypt_batch(bgn_mctx* m, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* r_be, size_t r_len,
                        uint8_t* out);
+/* bgn_encrypt_seeded_batch over the devices: the shard of elements [lo, hi) expands the indices first_index + lo ..,
+ * so the result does not depend on the number of devices. */
+int bgn_mencrypt_seeded_batch(bgn_mctx* m, size_t count, const uint8_t* x_be, size_t x_len, const uint8_t* seed32,
+                              uint64_t stream_id, uint64_t first_index, uint8_t* out);
 int bgn_madd_batch(bgn_mctx* m, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
                    size_t r_len, uint8_t* out);
 int bgn_msub_batch(bgn_mctx* m, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
@@ -460,7 +510,7 @@ double bgn_last_aux_kernel_ms(bgn_ctx* ctx);
 const char* bgn_last_aux_kernel_name(bgn_ctx* ctx);
 /* What the code object says about the kernel bgn_last_kernel_name names, when the engine knows its entry point
  * (the lane kernels: k_pairing<NL, 0|1>, k_g1_add_wire, k_gt_mul_wire, k_neg_wire, k_g1_add, k_gt_mul, k_g1_mul,
- * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response): out[0] = vector registers per lane, out[1] = scratch
+ * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response, k_random_scalars): out[0] = vector registers per lane, out[1] = scratch
  * (private-segment) bytes per lane, out[2] = static LDS bytes per workgroup, out[3] = threads per workgroup the
  * kernel may be launched with.  A kernel that is meant to hold everything in registers and has started to spill
  * shows here before it shows on a clock.  Returns BGN_E_ARG for a kernel it has no entry point of. */

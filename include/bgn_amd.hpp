@@ -480,6 +480,40 @@ class PublicKey {
           "bgn_encrypt_batch_dev");
     return out;
   }
+  // ---- randomness expanded on the device from a 32-byte seed the caller drew (bgn_amd.h "Randomness from a seed") ----
+  // row e = the scalar of (seed, stream_id, first_index + e) modulo n, n_len bytes each
+  std::vector<Scalar> RandomScalars(size_t count, const Bytes& seed, uint64_t stream_id = 0, uint64_t first_index = 0) const {
+    const size_t nl = N.size();
+    Bytes r(count * nl);
+    check(bgn_random_scalars_batch(h_, count, seed32(seed), stream_id, first_index, r.data()), "bgn_random_scalars_batch");
+    std::vector<Scalar> out(count);
+    for (size_t i = 0; i < count; ++i) out[i].assign(r.begin() + i * nl, r.begin() + (i + 1) * nl);
+    return out;
+  }
+  // Encrypt with Deterministic == false (bgn.go:334-337) for a batch: EncryptBatch(x, RandomScalars(...)), the rows never
+  // leaving the device.  Never the same (seed, stream_id, index) for two uses: count stream_id up per call.
+  std::vector<Ciphertext> EncryptBatchSeeded(const std::vector<Scalar>& x, const Bytes& seed, uint64_t stream_id = 0,
+                                             uint64_t first_index = 0) const {
+    size_t xl = 0;
+    Bytes xb = pack(x, xl), out(x.size() * E_);
+    check(bgn_encrypt_seeded_batch(h_, x.size(), xb.data(), xl, seed32(seed), stream_id, first_index, out.data()),
+          "bgn_encrypt_seeded_batch");
+    return split(out, false);
+  }
+  // the rows as a device array: r of the blinded *_dev calls (Width = n_len)
+  DeviceArray RandomScalarsDev(size_t count, const Bytes& seed, uint64_t stream_id = 0, uint64_t first_index = 0) const {
+    DeviceArray out(h_, count, N.size(), false);
+    check(bgn_random_scalars_batch_dev(h_, count, seed32(seed), stream_id, first_index, out.data(), nullptr),
+          "bgn_random_scalars_batch_dev");
+    return out;
+  }
+  DeviceArray EncryptBatchSeededDev(const DeviceArray& x, const Bytes& seed, uint64_t stream_id = 0,
+                                    uint64_t first_index = 0) const {
+    DeviceArray out(h_, x.Count, E_, false);
+    check(bgn_encrypt_seeded_batch_dev(h_, x.Count, x.data(), x.Width, seed32(seed), stream_id, first_index, out.data(), nullptr),
+          "bgn_encrypt_seeded_batch_dev");
+    return out;
+  }
   // operands of one level (lift with MakeL2BatchDev first where the reference would, bgn.go:444-452); the result may
   // be written over an operand with the *Into forms (accumulating, poly.go:171-207)
   DeviceArray AddBatchDev(const DeviceArray& a, const DeviceArray& b, const std::vector<Scalar>* r = nullptr,
@@ -839,6 +873,10 @@ class PublicKey {
     DeviceArray d(h_, v.size(), len, false);
     d.UploadBytes(b);
     return d;
+  }
+  static const uint8_t* seed32(const Bytes& seed) {
+    if (seed.size() != 32) throw std::invalid_argument("bgn_amd: the seed is 32 bytes");
+    return seed.data();
   }
   static Bytes pack(const std::vector<Scalar>& v, size_t& len) {
     len = 1;
