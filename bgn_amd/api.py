@@ -448,6 +448,15 @@ class Engine:
         check(self._lib.bgn_field_sums_batch(self._h, len(A), _ptr(A), _ptr(o)), "bgn_field_sums_batch")
         return o
 
+    def field_ops_family(self, family: int, xy: BytesLike):
+        """Diagnostics: (x*y || (x-y)*(x+y), x^2 || y^2, x+y || x-y) for elements x||y of plain residues, computed by the
+        multi-precision routines of one kernel family: 1 = cooperative, 2 = lane groups (bgn_field_ops_family_batch)."""
+        A = _as_u8(xy, self.elem_bytes)
+        o1, o2, o3 = self._out(len(A)), self._out(len(A)), self._out(len(A))
+        check(self._lib.bgn_field_ops_family_batch(self._h, int(family), len(A), _ptr(A), _ptr(o1), _ptr(o2), _ptr(o3)),
+              "bgn_field_ops_family_batch")
+        return o1, o2, o3
+
     def memory_bytes(self) -> int:
         """Device memory the context holds now (tables of the key + workspace)."""
         return int(self._lib.bgn_ctx_memory_bytes(self._h))

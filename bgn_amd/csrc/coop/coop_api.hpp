@@ -19,4 +19,9 @@ size_t coop_ws_words(int nl, size_t sw);
 bool coop_gt_pow_launch(int nl, hipStream_t s, const void* params, const uint32_t* a0, const uint32_t* a1, size_t sa,
                         const uint8_t* k, size_t kstride, size_t klen, uint32_t* o0, uint32_t* o1, size_t so, size_t count);
 const char* coop_pairing_kernel_name(int nl);
+// Diagnostics (bgn_field_ops_family_batch): the family's field arithmetic on its own, one element per wave.  xy canonical
+// Montgomery SoA (x in c0, y in c1); prod = (x*y, (x-y)*(x+y)), sqr = (x^2, y^2), lin = (x+y, x-y), plain canonical SoA.
+// Returns false when `nl` has no instantiation (the limb counts of the pairing kernel); count == 0 launches nothing and
+// only answers that.
+bool coop_field_ops_launch(int nl, hipStream_t s, const void* params, SoA2 xy, SoA2 prod, SoA2 sqr, SoA2 lin, size_t count);
 }  // namespace bgn

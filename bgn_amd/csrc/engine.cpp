@@ -3427,6 +3427,44 @@ int field_ops_common(bgn_ctx* c, size_t count, const uint8_t* xy, uint8_t* prod_
 }
 }  // namespace
 
+// The same view of the two split-limb families (coop/coop.hpp: a limb per lane of a wave; quad/quad.hpp: a quarter of
+// the limbs in each of four lanes), whose multi-precision arithmetic is their own: decode (shared) -> the family's
+// kernel -> encode (shared).  Host buffers only; never joins the combiner.
+int bgn_field_ops_family_batch(bgn_ctx* c, int family, size_t count, const uint8_t* xy, uint8_t* prod, uint8_t* sqr,
+                               uint8_t* lin) {
+  if (!c || (count && (!xy || !prod || !sqr || !lin))) return fail(BGN_E_ARG, "null argument");
+  if (family != 1 && family != 2) return fail(BGN_E_ARG, "family %d: 1 = cooperative, 2 = lane groups", family);
+  if (count > ((size_t)1 << 24)) return fail(BGN_E_ARG, "at most 2^24 elements");
+  const auto launch = family == 1 ? coop_field_ops_launch : quad_field_ops_launch;
+  if ((family == 1 && c->nl > 64) || !launch(c->nl, nullptr, nullptr, SoA2{}, SoA2{}, SoA2{}, SoA2{}, 0))
+    return fail(BGN_E_ARG, "the %s kernels have no instantiation for %d limbs", family == 1 ? "cooperative" : "lane-group", c->nl);
+  if (!count) return BGN_OK;
+  std::lock_guard<std::mutex> lk(c->mu);
+  hipStream_t s = nullptr;
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t st = round_up(count, 64), eb = (size_t)2 * c->L * count;
+  SoA2 X{}, O[3] = {};
+  uint8_t *din = nullptr, *dout[3] = {};
+  if (int rc = carve(c, [&](Ws& w) {
+    X = w.gt(st);
+    for (SoA2& o : O) o = w.gt(st);
+    din = (uint8_t*)w.cv.take(eb);
+    for (uint8_t*& d : dout) d = (uint8_t*)w.cv.take(eb);
+  })) return rc;
+  HIP_TRY(hipMemcpyAsync(din, xy, eb, hipMemcpyHostToDevice, s));
+  c->kt->decode(s, c->d_params, din, c->L, count, X, nullptr, nullptr);
+  launch(c->nl, s, c->d_params, X, O[0], O[1], O[2], count);
+  uint8_t* const host[3] = {prod, sqr, lin};
+  for (int i = 0; i < 3; ++i) {
+    c->kt->encode(s, nullptr, O[i].c0, O[i].c1, O[i].stride, c->L, count, dout[i]);
+    HIP_TRY(hipMemcpyAsync(host[i], dout[i], eb, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+
 // Page-locked host memory for the arrays of the host-buffer entry points: copies from and to it run at the full
 // PCIe rate (a pageable Go slice is staged by the runtime at roughly half of it).  bgn_host_free releases it.
 void* bgn_host_alloc(size_t bytes) {

@@ -269,6 +269,91 @@ bool quad_gt_pow_each_launch(int nl, hipStream_t s, const void* params, const ui
   return false;
 }
 
+// ---- field arithmetic on its own (bgn_field_ops_family_batch: the parity tests' direct view of quad_rows, quad_combo,
+// quad_normalize and quad_canonical; diagnostics, no operation runs on it) ---------------------------------------------
+// One element per quad, all four lanes of every quad active: a ragged tail computes stand-ins of the last element and
+// stores nothing.  xy: canonical Montgomery SoA (x in c0, y in c1); prod = (x*y, (x-y)*(x+y)), sqr = (x^2, y^2),
+// lin = (x+y, x-y), plain canonical SoA.  x and y lie in LDS as the interpreter's values do — a quad keeps its own
+// element, so a value takes a row block of its own: slots 0 and 4 with every lane's column as the base — and are read
+// by quad_load or, for x - y (+ p: y is below p) and x + y, by quad_combo + quad_normalize (quad_operand); a value
+// leaves Montgomery form by a product with the raw 1 before quad_canonical.  One loop with one call site of the
+// unrolled product, as everywhere: steps 0, 2, 4, 6 make a product, the step behind each and steps 8, 9 (the two sums)
+// take the value out.  Nothing of fpmont.hpp is called.
+constexpr int QUAD_FIELD_PER_BLOCK = QUAD_BLOCK / 4;
+constexpr u32 QUAD_FIELD_X = 0, QUAD_FIELD_Y = 4;
+
+template <int NL>
+__global__ void __launch_bounds__(QUAD_BLOCK)
+k_field_ops_quad(const FpParams<NL>* __restrict__ P, SoA2 xy, SoA2 prod, SoA2 sqr, SoA2 lin, size_t count) {
+  constexpr int M = QuadDims<NL>::M;
+  __shared__ u64 Vs[2 * QuadDims<NL>::MR * QUAD_BLOCK];
+  char* V = reinterpret_cast<char*>(Vs);
+  QuadLane<NL> c;
+  quad_lane_init<NL>(c, P);
+  c.base = (u32)threadIdx.x * 8u;
+  size_t e = (size_t)blockIdx.x * QUAD_FIELD_PER_BLOCK + (threadIdx.x >> 2);
+  const bool live = e < count;
+  if (!live) e = count - 1;
+  int t[M];
+  quad_gload<NL>(t, xy.c0, xy.stride, e, c.sub);
+  quad_store<NL>(V, quad_addr<NL>(QUAD_FIELD_X, c), t);
+  quad_gload<NL>(t, xy.c1, xy.stride, e, c.sub);
+  quad_store<NL>(V, quad_addr<NL>(QUAD_FIELD_Y, c), t);
+  constexpr u32 XY = QUAD_FIELD_X | QUAD_FIELD_Y << 8;
+  constexpr u32 PLUS = 0x0101u, MINUS = 0xFF01u;    // coefficients (1, 1) and (1, -1), a byte each
+#pragma unroll 1
+  for (int step = 0; step < 10; ++step) {           // every decision below is wave-uniform
+    const bool out = step >= 8 || (step & 1);
+    const int which = step < 8 ? step >> 1 : step - 4;
+    int a[M], b[M];
+    long long acc[M];
+    if (out) {
+      if (step >= 8) quad_operand<NL>(t, V, false, 2, XY, step == 8 ? PLUS : MINUS, step == 9, step == 9 ? 1 : 0, c);
+#pragma unroll
+      for (int j = 0; j < M; ++j) {
+        a[j] = t[j];
+        b[j] = (j == 0 && c.sub == 0) ? 1 : 0;
+      }
+    } else if (which == 0) {
+      quad_load<NL>(a, V, quad_addr<NL>(QUAD_FIELD_X, c));
+      quad_load<NL>(b, V, quad_addr<NL>(QUAD_FIELD_Y, c));
+    } else if (which == 1) {
+      quad_operand<NL>(a, V, false, 2, XY, MINUS, true, 1, c);
+      quad_operand<NL>(b, V, false, 2, XY, PLUS, false, 0, c);
+    } else {
+      quad_load<NL>(a, V, quad_addr<NL>(which == 2 ? QUAD_FIELD_X : QUAD_FIELD_Y, c));
+#pragma unroll
+      for (int j = 0; j < M; ++j) b[j] = a[j];
+    }
+#pragma unroll
+    for (int j = 0; j < M; ++j) acc[j] = 0;
+    quad_rows<NL>(acc, a, b, c, std::make_integer_sequence<int, NL>{});
+    quad_normalize<NL>(t, acc, c);
+    if (out) {
+      quad_canonical<NL>(t, c);
+      const SoA2& o = which < 2 ? prod : which < 4 ? sqr : lin;
+      if (live) quad_gstore<NL>((which & 1) ? o.c1 : o.c0, o.stride, e, c.sub, t);
+    }
+  }
+}
+
+template <int NL>
+static void launch_field(hipStream_t s, const void* params, SoA2 xy, SoA2 prod, SoA2 sqr, SoA2 lin, size_t count) {
+  hipLaunchKernelGGL((k_field_ops_quad<NL>), dim3((unsigned)((count + QUAD_FIELD_PER_BLOCK - 1) / QUAD_FIELD_PER_BLOCK)),
+                     dim3(QUAD_BLOCK), 0, s, (const FpParams<NL>*)params, xy, prod, sqr, lin, count);
+}
+
+bool quad_field_ops_launch(int nl, hipStream_t s, const void* params, SoA2 xy, SoA2 prod, SoA2 sqr, SoA2 lin, size_t count) {
+  switch (nl) {
+    case 10: if (count) launch_field<10>(s, params, xy, prod, sqr, lin, count); return true;
+    case 19: if (count) launch_field<19>(s, params, xy, prod, sqr, lin, count); return true;
+    case 36: if (count) launch_field<36>(s, params, xy, prod, sqr, lin, count); return true;
+    case 37: if (count) launch_field<37>(s, params, xy, prod, sqr, lin, count); return true;
+    case 72: if (count) launch_field<72>(s, params, xy, prod, sqr, lin, count); return true;
+  }
+  return false;
+}
+
 const char* quad_pairing_kernel_name(int nl) {
   switch (nl) {
     case 10: return "k_pairing_quad<10, 1>";

@@ -46,4 +46,9 @@ bool quad_gt_pow_each_launch(int nl, hipStream_t s, const void* params, const ui
                              uint32_t* ws);
 size_t quad_gt_pow_each_ws_words(int nl, size_t sw);
 const char* quad_pairing_kernel_name(int nl);
+// Diagnostics (bgn_field_ops_family_batch): the family's field arithmetic on its own, one element per quad of lanes.  xy
+// canonical Montgomery SoA (x in c0, y in c1); prod = (x*y, (x-y)*(x+y)), sqr = (x^2, y^2), lin = (x+y, x-y), plain
+// canonical SoA.  Returns false when `nl` has no instantiation (the limb counts of the pairing kernel); count == 0
+// launches nothing and only answers that.
+bool quad_field_ops_launch(int nl, hipStream_t s, const void* params, SoA2 xy, SoA2 prod, SoA2 sqr, SoA2 lin, size_t count);
 }  // namespace bgn

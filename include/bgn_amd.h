@@ -496,6 +496,18 @@ int bgn_field_ops_batch(bgn_ctx* ctx, size_t count, const uint8_t* xy, uint8_t* 
 /* The same for the sum of two products with ONE Montgomery reduction (csrc/fpmont.hpp fp_mul2: the a*b +- c*d of the
  * Miller steps since round 5): sums[e] = (x^2 + y^2) || (x*y + y^2). */
 int bgn_field_sums_batch(bgn_ctx* ctx, size_t count, const uint8_t* xy, uint8_t* sums);
+/* DIAGNOSTICS ONLY — no operation of the library runs on this entry point.  The same direct view for the two kernel
+ * families that split a field element over lanes and carry multi-precision arithmetic of their own: family 1 = the
+ * wave-cooperative kernels (csrc/coop/coop.hpp: one 29-bit limb per lane of a wave), family 2 = the lane groups
+ * (csrc/quad/quad.hpp: a quarter of the limbs in each of four lanes).  Between the shared decoder and encoder only the
+ * family's own routines run (product rows, operand sums, carry passes, canonical form).  xy: count elements x||y, L
+ * bytes each, any residues below p; the three outputs hold 2L bytes per element, canonical:
+ *   prod[e] = x*y || (x-y)*(x+y),   sqr[e] = x^2 || y^2,   lin[e] = x+y || x-y   (all mod p).
+ * Host buffers only; the call never joins the combiner.  BGN_E_ARG ("no instantiation") when the family has no kernels
+ * for the context's limb count: the cooperative kernels exist for 3, 10, 19, 36 and 37 limbs (they stop at the 64
+ * lanes of a wave), the lane groups for 10, 19, 36, 37 and 72 limbs. */
+int bgn_field_ops_family_batch(bgn_ctx* ctx, int family, size_t count, const uint8_t* xy, uint8_t* prod, uint8_t* sqr,
+                               uint8_t* lin);
 
 /* ---- measurement hooks (used by bench.py; not part of the drop-in surface) --- */
 /* Milliseconds spent in the dominant kernel of the most recent *_dev call on
