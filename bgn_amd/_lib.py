@@ -41,6 +41,7 @@ PROTOTYPES = {
     "bgn_add_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p]),
     "bgn_sub_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p]),
     "bgn_neg_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p]),
+    "bgn_sum_batch": (C.c_int, [_ctx, _sz, _sz, C.c_int, _u8p, _u8p, _sz, _u8p]),
     "bgn_mult_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _sz, _u8p]),
     "bgn_make_l2_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p]),
     "bgn_multconst_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _sz, _u8p, _sz, _u8p]),
@@ -67,6 +68,7 @@ PROTOTYPES = {
     "bgn_add_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_sub_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_neg_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, C.c_void_p]),
+    "bgn_sum_batch_dev": (C.c_int, [_ctx, _sz, _sz, C.c_int, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_mult_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_make_l2_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _u8p, C.c_void_p]),
     "bgn_multconst_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _sz, _u8p, _sz, _u8p, C.c_void_p]),

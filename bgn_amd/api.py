@@ -128,6 +128,22 @@ class Engine:
         check(self._lib.bgn_neg_batch(self._h, len(A), level, _ptr(A), _ptr(out)), "bgn_neg_batch")
         return out
 
+    def sum(self, level: int, ct: BytesLike, seg_len: int, r=None) -> np.ndarray:
+        """Segmented sum (bgn_sum_batch): `ct` holds nseg * seg_len elements row-major, row s of the result is the
+        sum of segment s (level 1: G1 addition, level 2: the GT product), blinded with one r per segment if given."""
+        A = _as_u8(ct, self.elem_bytes)
+        seg_len = int(seg_len)
+        if seg_len < 1 or len(A) % seg_len:
+            raise ValueError("the element count is not a multiple of seg_len")
+        nseg = len(A) // seg_len
+        rs = _scalars(r) if r is not None else None
+        if rs is not None and len(rs) != nseg:
+            raise ValueError("one blinding scalar per segment is required")
+        out = self._out(nseg)
+        check(self._lib.bgn_sum_batch(self._h, nseg, seg_len, level, _ptr(A), _ptr(rs), rs.shape[1] if rs is not None else 0,
+                                      _ptr(out)), "bgn_sum_batch")
+        return out
+
     def mult(self, a: BytesLike, b: BytesLike, r=None) -> np.ndarray:
         A, B = _as_u8(a, self.elem_bytes), _as_u8(b, self.elem_bytes)
         if len(A) != len(B):
@@ -271,6 +287,17 @@ class Engine:
         self._need("out", out, count * self.elem_bytes)
         check(self._lib.bgn_neg_batch_dev(self._h, count, level, a.data_ptr(), out.data_ptr(), self._stream()),
               "bgn_neg_batch_dev")
+
+    def sum_dev(self, level: int, ct, out, nseg: int, seg_len: int, r=None, r_len: int = 0) -> None:
+        """Device-resident segmented sum (bgn_sum_batch_dev): ct holds nseg * seg_len elements, out nseg; r (nseg x
+        r_len big-endian bytes on the device) blinds each sum.  Arrays at any byte address; `out` must not overlap
+        `ct`."""
+        self._need("ct", ct, nseg * seg_len * self.elem_bytes)
+        self._need("out", out, nseg * self.elem_bytes)
+        self._need("r", r, nseg * r_len)
+        check(self._lib.bgn_sum_batch_dev(self._h, nseg, seg_len, level, ct.data_ptr(),
+                                          r.data_ptr() if r is not None else None, r_len, out.data_ptr(),
+                                          self._stream()), "bgn_sum_batch_dev")
 
     def multconst_dev(self, level: int, a, k, k_len: int, out, count: Optional[int] = None, r=None, r_len: int = 0) -> None:
         """Device-resident MultConst (bgn.go:253-291): k holds count x k_len big-endian scalar bytes on the device;
@@ -876,6 +903,24 @@ class PublicKey:
             raise ValueError("AddBatch needs operands of one level")
         out = self.engine.add(lvl, b"".join(c.C for c in a), b"".join(c.C for c in b), self._r(len(a)))
         return [Ciphertext(bytes(row), lvl == 2) for row in out]
+
+    # -- sums: the loop of Add an aggregate is folded with (gadgets_test.go:24-46) as one engine call --
+    def SumBatch(self, rows: Sequence[Sequence[Ciphertext]]) -> List[Ciphertext]:
+        """One sum per row; the rows have one length and one level."""
+        rows = [list(r) for r in rows]
+        if not rows:
+            return []
+        seg_len = len(rows[0])
+        if seg_len == 0 or any(len(r) != seg_len for r in rows):
+            raise ValueError("SumBatch needs rows of one non-zero length")
+        lvl = self._lvl(rows[0][0])
+        if any(self._lvl(c) != lvl for r in rows for c in r):
+            raise ValueError("SumBatch needs operands of one level")
+        out = self.engine.sum(lvl, b"".join(c.C for r in rows for c in r), seg_len, self._r(len(rows)))
+        return [Ciphertext(bytes(row), lvl == 2) for row in out]
+
+    def Sum(self, cts: Sequence[Ciphertext]) -> Ciphertext:
+        return self.SumBatch([cts])[0]
 
     # -- MultConst: bgn.go:253-291 --
     def MultConst(self, c: Ciphertext, constant: int) -> Ciphertext:

@@ -209,4 +209,50 @@ inline size_t multconst_quad_limit(const DispatchView& v, int level, size_t klen
   return level == 1 ? 32768 : 24576;
 }
 
+// Segmented sums (sumops.hpp): nseg segments of seg_len elements are folded by reduction passes, pass k leaving
+// split[k] partials per segment (lane (s, t) of a pass accumulates the elements t, t + split, ... of segment s); the
+// last pass has split 1.  Two wishes pull at the choice: a chip wants `chip_lanes` lanes busy (level 1: 65536, one wave
+// on every SIMD; level 2: twice that), and a lane wants a run of at least `run_min` elements, over which its one
+// conversion per pass (level 1: the inversion that makes the Jacobian accumulator affine, about three additions'
+// worth) is spread.  While the array is large enough for both, a pass takes just the lanes that fill the chip and the
+// runs are as long as that leaves them; below, runs of run_min and fewer lanes — those passes are bound by the latency
+// of a run, and short runs in more passes beat long ones (1 x 2^20 at a 1024-bit key, run_min 2 / 4 / 8 / 16: level 1
+// 10.7 / 8.2 / 8.5 / 10.1 ms, level 2 0.92 / 1.01 / 1.26 / 1.83 ms, profiles/r10_sum_rates.csv; engine.cpp passes 4
+// and 2).
+// forced >= 1: the first pass's split, clamped to seg_len (a split equal to the length is a pass that only copies);
+// the passes behind it are planned.
+struct SumPlan {
+  int passes = 0;
+  uint32_t split[32] = {};
+};
+
+inline SumPlan plan_sum(size_t nseg, size_t seg_len, size_t chip_lanes, int64_t forced, int64_t run_min) {
+  SumPlan p;
+  if (!nseg || !seg_len) return p;
+  const size_t rmin = run_min < 2 ? 2 : (size_t)run_min;
+  if (!chip_lanes) chip_lanes = 1;
+  size_t len = seg_len;
+  for (;;) {
+    size_t split;
+    if (p.passes == 0 && forced >= 1) {
+      split = (size_t)forced < len ? (size_t)forced : len;
+    } else {
+      const size_t by_run = len / rmin;                                  // lanes per segment with runs of rmin
+      const size_t by_chip = (chip_lanes + nseg - 1) / nseg;              // lanes per segment that fill the chip
+      split = by_run < by_chip ? by_run : by_chip;
+      size_t pw = 1;
+      while (pw * 2 <= split) pw *= 2;                                   // whole workgroups, or whole segments per workgroup
+      split = pw;
+    }
+    p.split[p.passes++] = (uint32_t)split;
+    if (split == 1) break;
+    len = split;
+    if (p.passes == 31) {                                                // (never: a planned pass at least halves the length)
+      p.split[p.passes++] = 1;
+      break;
+    }
+  }
+  return p;
+}
+
 }  // namespace bgn

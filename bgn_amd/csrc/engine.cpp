@@ -1677,6 +1677,92 @@ int bgn_sub_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, con
   return addsub_dev(c, count, level, a, b, r_be, r_len, out, (hipStream_t)stream, true);
 }
 
+// ---- segmented sums --------------------------------------------------------------------------------------------
+// out[s] = ct[s*seg_len] + ... + ct[s*seg_len + seg_len - 1]: the loop of Add (bgn.go:442-497) the reference folds an
+// array with, as reduction passes from wire bytes to wire bytes (sumops.hpp) planned by dispatch.hpp plan_sum.  The
+// partials of a pass are wire arrays in the workspace, two of them in turns; the last pass writes `out`.  Blinded:
+// the last pass writes a workspace array instead, which takes one fixed-base product per SEGMENT through the path of
+// the blinded Add (blind_l1 / blind_l2) on its way to `out`.
+namespace {
+constexpr size_t kSumChipLanes = 65536;     // one wave on every SIMD
+
+int sum_check(const bgn_ctx* c, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be, size_t r_len,
+              const uint8_t* out) {
+  if (!c) return fail(BGN_E_ARG, "null argument");
+  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
+  if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
+  if (!nseg) return BGN_OK;
+  if (!seg_len) return fail(BGN_E_ARG, "seg_len == 0");
+  if (!ct || !out) return fail(BGN_E_ARG, "null argument");
+  if (seg_len > kMaxBatch || nseg > kMaxBatch / seg_len) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  return BGN_OK;
+}
+}  // namespace
+
+int bgn_sum_batch_dev(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
+                      size_t r_len, uint8_t* out, void* stream) {
+  if (int rc = sum_check(c, nseg, seg_len, level, ct, r_be, r_len, out)) return rc;
+  if (!nseg) return BGN_OK;
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->kt->sum_wire || (level == 2 && c->nl <= 40 && !c->d_barrett))
+    return fail(BGN_E_PARAM, "no sum kernel for these parameters");
+  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
+    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
+    if (rc) return rc;
+  }
+  // lanes a pass wants busy and the shortest run of a lane: the measured optimum per level at 2^20 elements of a 1024-bit
+  // key (profiles/r10_sum_rates.csv) — level 1 pays a conversion per lane per pass, level 2 only the partials' traffic
+  const int64_t want_lanes = opt(c, &Options::sum_lanes), want_run = opt(c, &Options::sum_run_min);
+  const SumPlan plan = plan_sum(nseg, seg_len, want_lanes > 0 ? (size_t)want_lanes : (level == 1 ? kSumChipLanes : 2 * kSumChipLanes),
+                                opt(c, &Options::sum_split), want_run > 0 ? want_run : (level == 1 ? 4 : 2));
+  const size_t E = 2 * (size_t)c->L;
+  size_t cap[2] = {0, 0};              // elements of the two arrays of partials
+  for (int k = 0; k + 1 < plan.passes; ++k)
+    if (nseg * plan.split[k] > cap[k & 1]) cap[k & 1] = nseg * plan.split[k];
+  const size_t st = round_up(nseg, 64);
+  uint8_t* part[2] = {nullptr, nullptr};
+  uint8_t* res = nullptr;
+  SoA2 O, T1, T2;
+  uint32_t* prefix = nullptr;
+  if (int rc = carve(c, [&](Ws& w) {
+    for (int i = 0; i < 2; ++i)
+      if (cap[i]) part[i] = (uint8_t*)w.cv.take(cap[i] * E + 16);
+    if (r_be) {
+      res = (uint8_t*)w.cv.take(nseg * E + 16);
+      if (level == 1) { O = w.g1(st); T1 = w.g1(st); T2 = w.g1(st); prefix = w.fp(st); }
+      else { O = w.gt(st); T1 = w.gt(st); T2 = w.gt(st); }
+    }
+  })) return rc;
+  const KernelTable* kt = c->kt;
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  const uint8_t* in = ct;
+  uint32_t len = (uint32_t)seg_len;
+  for (int k = 0; k < plan.passes; ++k) {
+    uint8_t* dst = k + 1 < plan.passes ? part[k & 1] : (r_be ? res : out);
+    kt->sum_wire(s, c->d_params, c->d_consts, c->d_barrett, level, in, c->L, nseg, len, plan.split[k], dst);
+    in = dst;
+    len = plan.split[k];
+  }
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->last_kernel = level == 1 ? "k_sum_g1_wire" : "k_sum_gt_wire";
+  c->ev_valid = true;
+  if (r_be) {                          // bgn.go:488-495 / :466-474, once per segment
+    kt->decode_plain(s, c->d_params, res, c->L, nseg, O);
+    if (level == 1) {
+      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, nseg);
+      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, nseg, out);
+    } else {
+      blind_l2(c, s, O, r_be, r_len, T1, T2, nseg);
+      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, nseg, out);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+
 int bgn_neg_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, uint8_t* out, void* stream) {
   if (!c || (count && (!a || !out))) return fail(BGN_E_ARG, "null argument");
   if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
@@ -2415,6 +2501,18 @@ int bgn_neg_batch(bgn_ctx* c, size_t count, int level, const uint8_t* a, uint8_t
   if (!count) return BGN_OK;
   const size_t E = 2 * (size_t)c->L;
   return host_call(c, COMB_NEG, level, {{a, nullptr, E, count}, {nullptr, out, E, count}});
+}
+
+// The rows of `ct` are whole segments, not elements: no CombineOp, the _dev entry point is the device side.
+int bgn_sum_batch(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be, size_t r_len,
+                  uint8_t* out) {
+  if (int rc = sum_check(c, nseg, seg_len, level, ct, r_be, r_len, out)) return rc;
+  if (!nseg) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0, {{ct, nullptr, seg_len * E, nseg}, {r_be, nullptr, r_len, nseg}, {nullptr, out, E, nseg}},
+                   [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_sum_batch_dev(c, nseg, seg_len, level, in[0], in[1], r_len, o[0], s);
+                   });
 }
 
 int bgn_multconst_batch(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint8_t* k_be, size_t k_len,

@@ -335,9 +335,14 @@ struct KernelTable {
   // of include/bgn_amd.h (randexp.hpp); the seed travels in the kernel arguments
   void (*random_scalars)(hipStream_t s, const void* params_n, RandSeed seed, uint64_t stream_id, uint64_t first_index,
                          size_t count, size_t n_len, uint8_t* out);
+  // one reduction pass of a segmented sum, wire bytes to wire bytes (sumops.hpp): nseg x len elements of `in` ->
+  // nseg x split elements of `out`, split <= len; level 1 G1 sums, level 2 GT products (`barrett` as for gt_mul_wire,
+  // not read beyond 40 limbs).  Either array at any byte address; they must not overlap.
+  void (*sum_wire)(hipStream_t s, const void* params, const PairingConsts* consts, const void* barrett, int level,
+                   const uint8_t* in, int L, size_t nseg, uint32_t len, uint32_t split, uint8_t* out);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
-  Entry entries[15];
+  Entry entries[18];
 };
 
 const KernelTable* kernel_table_nl3();

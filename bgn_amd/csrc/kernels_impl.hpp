@@ -11,6 +11,7 @@
 #include "sha256.hpp"
 #include "proofs.hpp"
 #include "randexp.hpp"
+#include "sumops.hpp"
 
 namespace bgn {
 
@@ -683,6 +684,120 @@ static void launch_gt_mul_wire(hipStream_t s, const void* params, const void* ba
 }
 #endif
 
+// ---- segmented sums (sumops.hpp): one reduction pass, wire bytes to wire bytes ----------------------------------
+// nseg x len elements of `in` -> nseg x split elements of `out` (partials, or the sums when split == 1).  `in` and
+// `out` may start at any byte address and must not overlap.  No __restrict__ on them: the host applies the pass to
+// its own partials, carved from one workspace.
+//
+// Level 2, up to 40 limbs: accumulator and element are four Fp in registers, the stage is the products' scratch —
+// the budget of k_gt_mul_wire (two waves per SIMD, two workgroups per CU).
+#if BGN_NL <= 40
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
+k_sum_gt_wire(const FpParams<NL>* __restrict__ P, const BarrettParams<NL>* __restrict__ Bp, const uint8_t* in, int L,
+              size_t nseg, u32 len, u32 split, uint8_t* out) {
+  constexpr int SWORDS = SumStage<NL>::WORDS > NL * FP_BLOCK ? SumStage<NL>::WORDS : NL * FP_BLOCK;
+  __shared__ alignas(16) u32 sw[SWORDS];
+  const size_t EB = (size_t)(2 * L);
+  const u32 tid = threadIdx.x;
+  const SumLane ln = sum_lane((size_t)blockIdx.x, tid, nseg, split);
+  const u32 rsw = sum_run_words(split, EB);
+  const u32 steps = sum_steps(len, split);
+  Fp<NL> acc0, acc1;
+  fp_zero(acc0);
+  fp_zero(acc1);
+  acc0.v[0] = 1;
+#pragma unroll 1
+  for (u32 j = 0; j < steps; ++j) {
+    const u32 n = sum_run_len(ln, j, len, split);         // workgroup-uniform
+    if (!n) break;
+    __syncthreads();                                      // the previous product's scratch is done with
+    const size_t first = ln.seg0 * (size_t)len + (size_t)j * split + ln.t0;
+    const u32 roff = sum_stage_in<NL>(sw, in, first, (size_t)len, ln.nruns, ln.ok ? ln.run : 0u, n, rsw, EB);
+    const bool live = ln.ok && ln.t - ln.t0 < n;
+    Fp<NL> b0, b1;
+    sum_decode<NL>(b0, b1, sw, roff + (live ? (ln.t - ln.t0) * (u32)EB : 0u), L);   // idle lanes decode a valid element: discarded
+    sum_gt_take<NL>(b0, b1, live, P, Bp);
+    __syncthreads();                                      // every lane has read its element: the stage is scratch now
+    if (j == 0) {
+      acc0 = b0;
+      acc1 = b1;
+    } else {
+      sum_gt_step<NL>(acc0, acc1, b0, b1, P, Bp, sw + tid, FP_BLOCK);
+    }
+  }
+  __syncthreads();                                        // ... and becomes the stage of the partials
+  const u32 nout = ln.nruns * ln.width;
+  uint8_t* g = out + (ln.seg0 * (size_t)split + ln.t0) * EB;
+  if (ln.ok) sum_encode<NL>(sw, g, tid, L, acc0, acc1);
+  wire_stage_out<NL>(reinterpret_cast<const WireStage<NL>*>(sw), g, (size_t)nout * EB);
+}
+#endif
+
+// Level 1 (LEVEL == 1: Jacobian accumulator) and, beyond 40 limbs, level 2 (LEVEL == 2: Montgomery accumulator).
+// LDS: the four slots of the accumulation; the stage lies over the two scratch slots L[0], L[1], which nothing needs
+// while a slice is staged and decoded (barriers on both sides).
+template <int NL, int LEVEL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_sum_acc_wire(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, const uint8_t* in, int L,
+               size_t nseg, u32 len, u32 split, uint8_t* out) {
+  constexpr int LW = (int)(sizeof(LFp<NL>) / 4);
+  constexpr int FRONT = SumStage<NL>::WORDS > 2 * LW ? SumStage<NL>::WORDS : 2 * LW;
+  __shared__ alignas(16) u32 sw[FRONT + 2 * LW];
+  LFp<NL>* Ls = reinterpret_cast<LFp<NL>*>(sw + (FRONT - 2 * LW));
+  const size_t EB = (size_t)(2 * L);
+  const u32 tid = threadIdx.x;
+  const SumLane ln = sum_lane((size_t)blockIdx.x, tid, nseg, split);
+  const u32 rsw = sum_run_words(split, EB);
+  const u32 steps = sum_steps(len, split);
+  JacAcc<NL> S;                                           // LEVEL 2: X, Y are the accumulator's re, im
+  bool acc_inf = true;
+  if (LEVEL == 1) sum_g1_init<NL>(S, acc_inf, P);
+  else sum_gt_mont_init<NL>(S.X, S.Y, P);
+#pragma unroll 1
+  for (u32 j = 0; j < steps; ++j) {
+    const u32 n = sum_run_len(ln, j, len, split);         // workgroup-uniform
+    if (!n) break;
+    __syncthreads();                                      // every lane is done with the scratch slots
+    const size_t first = ln.seg0 * (size_t)len + (size_t)j * split + ln.t0;
+    const u32 roff = sum_stage_in<NL>(sw, in, first, (size_t)len, ln.nruns, ln.ok ? ln.run : 0u, n, rsw, EB);
+    const bool live = ln.ok && ln.t - ln.t0 < n;
+    Fp<NL> x, y;
+    sum_decode<NL>(x, y, sw, roff + (live ? (ln.t - ln.t0) * (u32)EB : 0u), L);
+    __syncthreads();                                      // every lane has read its element
+    if (LEVEL == 1) sum_g1_step<NL>(S, acc_inf, x, y, live, Ls, P);
+    else sum_gt_mont_step<NL>(S.X, S.Y, x, y, live, Ls, P);
+  }
+  Fp<NL> x, y;
+  if (LEVEL == 1) sum_g1_finish<NL>(x, y, S, acc_inf, Ls, C, P);
+  else sum_gt_mont_finish<NL>(x, y, S.X, S.Y, Ls, P);
+  __syncthreads();                                        // the scratch slots become the stage of the partials
+  const u32 nout = ln.nruns * ln.width;
+  uint8_t* g = out + (ln.seg0 * (size_t)split + ln.t0) * EB;
+  if (ln.ok) sum_encode<NL>(sw, g, tid, L, x, y);
+  wire_stage_out<NL>(reinterpret_cast<const WireStage<NL>*>(sw), g, (size_t)nout * EB);
+}
+
+static void launch_sum_wire(hipStream_t s, const void* params, const PairingConsts* consts, const void* barrett, int level,
+                            const uint8_t* in, int L, size_t nseg, uint32_t len, uint32_t split, uint8_t* out) {
+  if (!nseg || !len || !split) return;
+  if (split > len) split = len;                           // every lane of a pass owns at least one element
+  const dim3 grid((unsigned)sum_blocks(nseg, split));
+  if (level == 1) {
+    hipLaunchKernelGGL((k_sum_acc_wire<NL_, 1>), grid, dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params, consts, in, L, nseg,
+                       len, split, out);
+    return;
+  }
+#if BGN_NL <= 40
+  hipLaunchKernelGGL(k_sum_gt_wire<NL_>, grid, dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                     (const BarrettParams<NL_>*)barrett, in, L, nseg, len, split, out);
+#else
+  (void)barrett;
+  hipLaunchKernelGGL((k_sum_acc_wire<NL_, 2>), grid, dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params, consts, in, L, nseg,
+                     len, split, out);
+#endif
+}
+
 template <int NL>
 __global__ void __launch_bounds__(FP_BLOCK)
 k_gt_pow(const FpParams<NL>* __restrict__ P, GtPowArgs A) {
@@ -1329,6 +1444,7 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
       launch_challenge,
       launch_pok_response,
       launch_random_scalars,
+      launch_sum_wire,
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1344,6 +1460,12 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
        {"k_challenge", (const void*)k_challenge<NL_>},
        {"k_pok_response", (const void*)k_pok_response<NL_>},
        {"k_random_scalars", (const void*)k_random_scalars<NL_>},
+       {"k_sum_g1_wire", (const void*)k_sum_acc_wire<NL_, 1>},
+#if BGN_NL <= 40
+       {"k_sum_gt_wire", (const void*)k_sum_gt_wire<NL_>},
+#else
+       {"k_sum_gt_wire", (const void*)k_sum_acc_wire<NL_, 2>},
+#endif
        {nullptr, nullptr}},
   };
   return &t;

@@ -52,6 +52,12 @@ struct Options {
   V l1_fused{1};           // deterministic level-1 Add / Sub in one wire-to-wire launch (0: decode, decode, k_g1_add, encode)
   V l2_fused{1};           // deterministic level-2 Add / Sub in one wire-to-wire launch (0: decode, decode, k_gt_mul, encode)
   V multconst_l2_ladder{1};// MultConst on level-2 ciphertexts by the norm-1 ladder where the norm is 1 (0: general power)
+  V sum_split{-1};         // segmented sums: partials per segment after the first reduction pass (-1: planned, dispatch.hpp
+                           // plan_sum; k >= 1: forced, clamped to the segment length — same bytes)
+  V sum_run_min{0};        // ... and the shortest run of elements a lane of a planned pass accumulates (0: 4 on level 1, 2 on
+                           // level 2 — profiles/r10_sum_rates.csv; otherwise at least 2)
+  V sum_lanes{0};          // ... and the lanes a planned pass wants busy (0: 65536 on level 1, one wave per SIMD; 131072 on
+                           // level 2, whose pass runs two waves per SIMD)
   V poly_karatsuba{1};     // Karatsuba levels on square MultPoly products
   V poly_levels{-1};       // forced number of levels (-1: planned)
   V poly_tables{-1};       // per-coefficient line tables: 0 never, 1 always, -1 by size
@@ -120,6 +126,9 @@ inline const OptionDesc* option_table(size_t* n) {
       {"l1_fused", &Options::l1_fused, true, nullptr},
       {"l2_fused", &Options::l2_fused, true, nullptr},
       {"multconst_l2_ladder", &Options::multconst_l2_ladder, true, nullptr},
+      {"sum_split", &Options::sum_split, true, nullptr},
+      {"sum_run_min", &Options::sum_run_min, true, nullptr},
+      {"sum_lanes", &Options::sum_lanes, true, nullptr},
       {"poly_karatsuba", &Options::poly_karatsuba, true, nullptr},
       {"poly_levels", &Options::poly_levels, true, nullptr},
       {"poly_tables", &Options::poly_tables, true, nullptr},

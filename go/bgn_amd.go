@@ -338,6 +338,26 @@ func (e *Engine) SubBatch(a, b []*Ciphertext, l2 bool, r []*big.Int) ([]*Ciphert
 	return e.addSub(a, b, l2, r, true)
 }
 
+// SumBatch folds len(a)/segLen segments of segLen consecutive ciphertexts each into one sum per segment: the loop of
+// pk.Add (bgn.go:442-497) an aggregate is computed with (gadgets_test.go:24-46) as one call (bgn_sum_batch).  r: one
+// blinding scalar per segment in non-deterministic mode.
+func (e *Engine) SumBatch(a []*Ciphertext, segLen int, l2 bool, r []*big.Int) ([]*Ciphertext, error) {
+	if segLen < 1 || len(a)%segLen != 0 {
+		return nil, errors.New("bgn_amd: the element count is not a multiple of segLen")
+	}
+	nseg := len(a) / segLen
+	A := e.pack(a)
+	rb, rw := e.randomness(r)
+	out := make([]byte, nseg*2*e.L)
+	err := locked(func() C.int {
+		return C.bgn_sum_batch(e.h, C.size_t(nseg), C.size_t(segLen), levelOf(l2), u8(A), u8(rb), C.size_t(rw), u8(out))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return e.unpack(out, l2), nil
+}
+
 // NegBatch is pk.Neg (bgn.go:436-438) in deterministic mode.
 func (e *Engine) NegBatch(a []*Ciphertext, l2 bool) ([]*Ciphertext, error) {
 	A := e.pack(a)
@@ -901,6 +921,32 @@ func (e *Engine) AddBatchDev(a, b *DeviceArray, r []*big.Int) (*DeviceArray, err
 // SubBatchDev is pk.Sub over device arrays (bgn.go:375-432; bgn_sub_batch_dev).
 func (e *Engine) SubBatchDev(a, b *DeviceArray, r []*big.Int) (*DeviceArray, error) {
 	return e.addSubDev(a, b, r, true)
+}
+
+// SumBatchDev is SumBatch over a device array of nseg*segLen elements (bgn_sum_batch_dev): the sums stay on the device.
+func (e *Engine) SumBatchDev(a *DeviceArray, segLen int, r []*big.Int) (*DeviceArray, error) {
+	if segLen < 1 || a.Count%segLen != 0 {
+		return nil, errors.New("bgn_amd: the element count is not a multiple of segLen")
+	}
+	nseg := a.Count / segLen
+	rb, rw := e.randomness(r)
+	dr, err := e.uploadScalars(rb, nseg, rw)
+	if err != nil {
+		return nil, err
+	}
+	defer dr.Free()
+	out, err := e.likeOut(nseg, a.L2)
+	if err != nil {
+		return nil, err
+	}
+	err = locked(func() C.int {
+		return C.bgn_sum_batch_dev(e.h, C.size_t(nseg), C.size_t(segLen), levelOf(a.L2), a.u8(), dr.ptrOrNil(), C.size_t(rw), out.u8(), nil)
+	})
+	if err != nil {
+		out.Free()
+		return nil, err
+	}
+	return out, nil
 }
 
 // NegBatchDev is pk.Neg over a device array (bgn.go:436-438; bgn_neg_batch_dev).

@@ -231,6 +231,23 @@ int bgn_sub_batch(bgn_ctx* ctx, size_t count, int level, const uint8_t* a, const
 /* out[i] = -a[i].  Replaces Neg (bgn.go:436-438) in deterministic mode. */
 int bgn_neg_batch(bgn_ctx* ctx, size_t count, int level, const uint8_t* a, uint8_t* out);
 
+/* Segmented sum: out[s] = ct[s*seg_len] + ... + ct[s*seg_len + seg_len - 1] for s < nseg — G1 addition on level 1,
+ * the F_p^2 product on level 2 — blinded with Q^r[s] resp. e(Q,Q)^r[s] when r != NULL (one row of r_len bytes per
+ * SEGMENT: one fixed-base product per result, not one per addition as a loop of blinded Adds pays).
+ * ct: nseg*seg_len elements, row-major; out: nseg elements; out must not overlap ct.  nseg == 0 is BGN_OK; seg_len == 0
+ * or nseg*seg_len above 2^28 is BGN_E_ARG; seg_len == 1 copies (and blinds).  The input contract is Add's: level 1
+ * takes valid points or the identity (all zero, in and out), level 2 reduces residues >= p first and its identity is
+ * 1 || 0.  The result is canonical wire bytes and — the group law being associative and commutative — does not
+ * depend on the order of accumulation, which the engine chooses: reduction passes from wire bytes to wire bytes, each
+ * lane folding a strided run of its segment, the partials of a pass in the workspace (options sum_split, sum_run_min, sum_lanes;
+ * csrc/sumops.hpp).  The device form takes arrays at any byte address.  Neither form joins the combiner of concurrent
+ * small calls.  2^20 device-resident elements of a 1024-bit key as one segment: level 2 in 0.92 ms (the halving tree of
+ * twenty bgn_add_batch_dev launches: 1.15 ms), level 1 in 8.2 ms (the tree: 8.0 ms); 65536 segments of 16: 0.53 ms and
+ * 2.4 ms (profiles/r10_sum_rates.csv).
+ * Replaces the loop of Add (bgn.go:442-497) an aggregate is folded with (gadgets_test.go:24-46). */
+int bgn_sum_batch(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
+                  size_t r_len, uint8_t* out);
+
 /* out[i] = e(a[i], b[i]) (* e(Q,Q)^r[i] when r != NULL); inputs level 1, output level 2.
  * Replaces Mult (bgn.go:294-314). */
 int bgn_mult_batch(bgn_ctx* ctx, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be, size_t r_len,
@@ -350,6 +367,8 @@ int bgn_add_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* a, c
 int bgn_sub_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
                       size_t r_len, uint8_t* out, void* stream);
 int bgn_neg_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* a, uint8_t* out, void* stream);
+int bgn_sum_batch_dev(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
+                      size_t r_len, uint8_t* out, void* stream);
 int bgn_mult_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
                        size_t r_len, uint8_t* out, void* stream);
 int bgn_make_l2_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* a, uint8_t* out, void* stream);
@@ -522,7 +541,7 @@ double bgn_last_aux_kernel_ms(bgn_ctx* ctx);
 const char* bgn_last_aux_kernel_name(bgn_ctx* ctx);
 /* What the code object says about the kernel bgn_last_kernel_name names, when the engine knows its entry point
  * (the lane kernels: k_pairing<NL, 0|1>, k_g1_add_wire, k_gt_mul_wire, k_neg_wire, k_g1_add, k_gt_mul, k_g1_mul,
- * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response, k_random_scalars): out[0] = vector registers per lane, out[1] = scratch
+ * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response, k_random_scalars, k_sum_g1_wire, k_sum_gt_wire): out[0] = vector registers per lane, out[1] = scratch
  * (private-segment) bytes per lane, out[2] = static LDS bytes per workgroup, out[3] = threads per workgroup the
  * kernel may be launched with.  A kernel that is meant to hold everything in registers and has started to spill
  * shows here before it shows on a clock.  Returns BGN_E_ARG for a kernel it has no entry point of. */

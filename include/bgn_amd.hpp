@@ -456,6 +456,18 @@ class PublicKey {
           subtract ? "bgn_sub_batch" : "bgn_add_batch");
     return split(out, level == 2);
   }
+  // Segmented sum (bgn_sum_batch): a.size() / seg_len sums of seg_len consecutive elements each — the loop of Add
+  // (bgn.go:442-497) an aggregate is folded with; r: one blinding scalar per segment.
+  std::vector<Ciphertext> SumBatch(const std::vector<Ciphertext>& a, size_t seg_len, const std::vector<Scalar>* r = nullptr) const {
+    if (!seg_len || a.size() % seg_len) throw Error(BGN_E_ARG, "the element count is not a multiple of seg_len");
+    const int level = a.empty() || !a[0].L2 ? 1 : 2;
+    const size_t nseg = a.size() / seg_len;
+    size_t rl = 0;
+    Bytes A = join(a), rb, out(nseg * E_);
+    if (r) rb = pack(*r, rl);
+    check(bgn_sum_batch(h_, nseg, seg_len, level, A.data(), r ? rb.data() : nullptr, rl, out.data()), "bgn_sum_batch");
+    return split(out, level == 2);
+  }
   std::vector<Ciphertext> MultBatch(const std::vector<Ciphertext>& a, const std::vector<Ciphertext>& b,
                                     const std::vector<Scalar>* r = nullptr) const {
     size_t rl = 0;
@@ -531,6 +543,17 @@ class PublicKey {
     check((subtract ? bgn_sub_batch_dev : bgn_add_batch_dev)(h_, a.Count, a.L2 ? 2 : 1, a.data(), b.data(),
                                                              r ? dr.data() : nullptr, rl, out.data(), nullptr),
           subtract ? "bgn_sub_batch_dev" : "bgn_add_batch_dev");
+  }
+  // bgn_sum_batch_dev over a device array of nseg * seg_len elements: nseg sums, left on the device.
+  DeviceArray SumBatchDev(const DeviceArray& a, size_t seg_len, const std::vector<Scalar>* r = nullptr) const {
+    if (!seg_len || a.Count % seg_len) throw Error(BGN_E_ARG, "the element count is not a multiple of seg_len");
+    const size_t nseg = a.Count / seg_len;
+    size_t rl = 0;
+    DeviceArray dr, out(h_, nseg, E_, a.L2);
+    if (r) dr = scalars_dev(*r, rl);
+    check(bgn_sum_batch_dev(h_, nseg, seg_len, a.L2 ? 2 : 1, a.data(), r ? dr.data() : nullptr, rl, out.data(), nullptr),
+          "bgn_sum_batch_dev");
+    return out;
   }
   DeviceArray NegBatchDev(const DeviceArray& a) const {
     DeviceArray out(h_, a.Count, E_, a.L2);
