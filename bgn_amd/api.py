@@ -144,6 +144,33 @@ class Engine:
                                       _ptr(out)), "bgn_sum_batch")
         return out
 
+    def lincomb(self, level: int, ct: BytesLike, W, w_bits: Optional[int] = None, r=None, nvec: int = 1) -> np.ndarray:
+        """Linear map (bgn_lincomb_batch): `ct` holds nvec vectors of d elements, `W` is an integer nrows x d array of
+        plaintext weights; row v*nrows + i of the result is sum_j W[i][j] * ct[v][j] (level 1: G1, level 2: powers and
+        products in GT), blinded with one r per result if given.  w_bits: the bound on |W| in bits (default: the bit
+        length of the largest |W|); a weight counts as sign(w) * (|w| mod 2^w_bits)."""
+        A = _as_u8(ct, self.elem_bytes)
+        Wa = np.asarray(W)
+        if Wa.ndim != 2 or Wa.dtype.kind not in "iu":
+            raise ValueError("W must be a two-dimensional integer array")
+        nrows, d = Wa.shape
+        nvec = int(nvec)
+        if d < 1 or nvec < 0 or len(A) != nvec * d:
+            raise ValueError("ct must hold nvec vectors of as many elements as W has columns")
+        top = int(np.abs(Wa.astype(np.int64)).max()) if Wa.size else 0
+        if top > 0x7FFFFFFF:
+            raise ValueError("weights must fit 31 bits and a sign")
+        if w_bits is None:
+            w_bits = max(1, top.bit_length())
+        Wa = np.ascontiguousarray(Wa, dtype=np.int32)
+        rs = _scalars(r) if r is not None else None
+        if rs is not None and len(rs) != nvec * nrows:
+            raise ValueError("one blinding scalar per result is required")
+        out = self._out(nvec * nrows)
+        check(self._lib.bgn_lincomb_batch(self._h, nvec, nrows, d, level, _ptr(A), _ptr(Wa), int(w_bits), _ptr(rs),
+                                          rs.shape[1] if rs is not None else 0, _ptr(out)), "bgn_lincomb_batch")
+        return out
+
     def mult(self, a: BytesLike, b: BytesLike, r=None) -> np.ndarray:
         A, B = _as_u8(a, self.elem_bytes), _as_u8(b, self.elem_bytes)
         if len(A) != len(B):
@@ -298,6 +325,18 @@ class Engine:
         check(self._lib.bgn_sum_batch_dev(self._h, nseg, seg_len, level, ct.data_ptr(),
                                           r.data_ptr() if r is not None else None, r_len, out.data_ptr(),
                                           self._stream()), "bgn_sum_batch_dev")
+
+    def lincomb_dev(self, level: int, ct, w, w_bits: int, out, nvec: int, nrows: int, d: int, r=None, r_len: int = 0) -> None:
+        """Device-resident linear map (bgn_lincomb_batch_dev): ct holds nvec * d elements, w nrows * d int32 weights
+        (4-byte aligned), out nvec * nrows elements; r (nvec * nrows x r_len big-endian bytes on the device) blinds
+        each result.  ct and out at any byte address; `out` must not overlap `ct` or `w`."""
+        self._need("ct", ct, nvec * d * self.elem_bytes)
+        self._need("w", w, nrows * d * 4)
+        self._need("out", out, nvec * nrows * self.elem_bytes)
+        self._need("r", r, nvec * nrows * r_len)
+        check(self._lib.bgn_lincomb_batch_dev(self._h, nvec, nrows, d, level, ct.data_ptr(), w.data_ptr(), int(w_bits),
+                                              r.data_ptr() if r is not None else None, r_len, out.data_ptr(),
+                                              self._stream()), "bgn_lincomb_batch_dev")
 
     def multconst_dev(self, level: int, a, k, k_len: int, out, count: Optional[int] = None, r=None, r_len: int = 0) -> None:
         """Device-resident MultConst (bgn.go:253-291): k holds count x k_len big-endian scalar bytes on the device;
@@ -921,6 +960,22 @@ class PublicKey:
 
     def Sum(self, cts: Sequence[Ciphertext]) -> Ciphertext:
         return self.SumBatch([cts])[0]
+
+    # -- linear maps: the loops of MultConst + Add (bgn.go:253-291, :442-497) over a shared vector as one engine call --
+    def LinCombBatch(self, W, cts: Sequence[Ciphertext]) -> List[Ciphertext]:
+        """out[i] = sum_j W[i][j] * cts[j] for an integer matrix W (negative weights subtract); one level."""
+        cts = list(cts)
+        Wa = np.asarray(W)
+        if Wa.ndim != 2 or Wa.shape[1] != len(cts) or not cts:
+            raise ValueError("LinCombBatch needs a matrix with one column per ciphertext")
+        lvl = self._lvl(cts[0])
+        if any(self._lvl(c) != lvl for c in cts):
+            raise ValueError("LinCombBatch needs operands of one level")
+        out = self.engine.lincomb(lvl, b"".join(c.C for c in cts), Wa, r=self._r(Wa.shape[0]))
+        return [Ciphertext(bytes(row), lvl == 2) for row in out]
+
+    def LinComb(self, weights: Sequence[int], cts: Sequence[Ciphertext]) -> Ciphertext:
+        return self.LinCombBatch([list(weights)], cts)[0]
 
     # -- MultConst: bgn.go:253-291 --
     def MultConst(self, c: Ciphertext, constant: int) -> Ciphertext:

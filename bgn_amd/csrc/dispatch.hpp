@@ -255,4 +255,87 @@ inline SumPlan plan_sum(size_t nseg, size_t seg_len, size_t chip_lanes, int64_t 
   return p;
 }
 
+// Linear maps (linops.hpp): out[v][r] = sum_j w[r][j] * ct[v][j] over nvec vectors of d ciphertexts and nrows rows of
+// weights below 2^w_bits.  Two choices, neither of which any byte depends on:
+//   omega   the window width, 1 .. 8.  A table of the multiples 1 .. H = 2^(omega-1) of every ciphertext costs
+//           ncols * (H-1) table steps (ncols = nvec*d, one lane per ciphertext) and has to fit `budget_bytes` at
+//           `entry_bytes` per entry, and 2^28 entries (gmem.hpp); the walk then costs every output d * nwin additions
+//           and (nwin-1) * omega doublings, nwin = ceil((w_bits+1) / omega).  omega = 1 needs no table.
+//   nchunk  the chunks the columns of one output are cut into, each a lane of its own whose partial the passes of
+//           plan_sum fold afterwards: as many as fill `chip_lanes` lanes, while a chunk keeps at least kLinMinRun columns
+//           to spread its doublings and its one inversion over.
+// Costs are in rounds of the chip: work that fits the chip's lanes once takes as long as one lane's.  The unit is one
+// F_p product: a mixed addition 13, a doubling 9, a table step 13 + 6 (the entry's share of the shared inversion), a
+// lane's conversion about 40; level 2: a product in F_p^2 3, a squaring 2, no conversion.
+// forced_window in 1 .. 8 and forced_split >= 1 override (the window narrowed until its table fits; the split clamped
+// to d and to 2^28 partials).
+constexpr size_t kLinMinRun = 8;
+// (this header includes nothing of the kernels': the widest window and the window count are restated from linrecode.hpp,
+// and tests/cpp/lin_recode_test.cpp holds the two against each other)
+constexpr int kLinPlanMaxWindow = 8;
+inline int lin_plan_windows(int w_bits, int omega) { return (w_bits + omega) / omega; }      // ceil((w_bits + 1) / omega)
+struct LinCost {
+  double c_table, c_add, c_dbl, c_fin;
+};
+inline LinCost lin_cost(int level) { return level == 1 ? LinCost{19, 13, 9, 40} : LinCost{3, 3, 2, 2}; }
+
+struct LinPlan {
+  int omega = 0, nwin = 0;
+  size_t nchunk = 0;
+  size_t entries = 0;           // table entries (0 at omega = 1)
+};
+
+inline size_t lin_table_entries(size_t ncols, int omega) { return omega > 1 ? ncols << (omega - 1) : 0; }
+
+inline LinPlan plan_lincomb(size_t nvec, size_t nrows, size_t d, int w_bits, size_t budget_bytes, size_t entry_bytes,
+                            int level, size_t chip_lanes, int64_t forced_window, int64_t forced_split) {
+  LinPlan p;
+  if (!nvec || !nrows || !d || w_bits < 1 || w_bits > 31) return p;
+  if (!chip_lanes) chip_lanes = 1;
+  const size_t ncols = nvec * d, nout = nvec * nrows;
+  // chunks
+  size_t nchunk = 1;
+  if (forced_split >= 1) {
+    nchunk = (size_t)forced_split;
+  } else if (nout < chip_lanes) {
+    const size_t by_chip = (chip_lanes + nout - 1) / nout, by_run = d / kLinMinRun;
+    nchunk = by_run < by_chip ? by_run : by_chip;
+  }
+  if (nchunk > d) nchunk = d;
+  if (nchunk > kMaxBatch / nout) nchunk = kMaxBatch / nout;
+  if (nchunk < 1) nchunk = 1;
+  p.nchunk = nchunk;
+  // window
+  const LinCost k = lin_cost(level);
+  const auto fits = [&](int omega) {
+    const size_t e = lin_table_entries(ncols, omega);
+    return omega == 1 || (e <= kMaxBatch && entry_bytes <= budget_bytes && e <= budget_bytes / entry_bytes);
+  };
+  const auto rounds = [&](size_t lanes) { return (double)((lanes + chip_lanes - 1) / chip_lanes); };
+  int best = 1;
+  if (forced_window >= 1) {
+    best = forced_window > kLinPlanMaxWindow ? kLinPlanMaxWindow : (int)forced_window;
+    while (!fits(best)) --best;
+  } else {
+    double best_cost = 0;
+    for (int omega = 1; omega <= kLinPlanMaxWindow; ++omega) {
+      if (!fits(omega)) break;
+      const int nwin = lin_plan_windows(w_bits, omega);
+      const double H = (double)((size_t)1 << (omega - 1));
+      const double run = (double)((d + nchunk - 1) / nchunk);
+      const double table = omega > 1 ? rounds(ncols) * (H - 1) * k.c_table : 0;
+      const double walk = rounds(nout * nchunk) * (run * nwin * k.c_add + (double)(nwin - 1) * omega * k.c_dbl + k.c_fin);
+      const double cost = table + walk;
+      if (omega == 1 || cost < best_cost) {
+        best = omega;
+        best_cost = cost;
+      }
+    }
+  }
+  p.omega = best;
+  p.nwin = lin_plan_windows(w_bits, best);
+  p.entries = lin_table_entries(ncols, best);
+  return p;
+}
+
 }  // namespace bgn

@@ -32,6 +32,7 @@ namespace {
 int ensure_arena(bgn_ctx* c, size_t bytes);      // (carve.hpp grows the workspace through it)
 }
 #include "carve.hpp"
+#include "linrecode.hpp"
 
 using namespace bgn;
 
@@ -1763,6 +1764,133 @@ int bgn_sum_batch_dev(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const 
   return BGN_OK;
 }
 
+// ---- linear maps of ciphertext vectors ---------------------------------------------------------------------------
+// out[v][r] = sum_j w[r][j] * ct[v][j] with plaintext weights (linops.hpp), planned by dispatch.hpp plan_lincomb: the
+// vectors are decoded once, the weights recoded into digit planes, a window table built per ciphertext (none at window
+// width 1) and walked by one lane per (output, column chunk).  The lanes' results are encoded to wire bytes; with more
+// than one chunk they are partials that the passes of the segmented sum fold (seg_len = nchunk).  Blinding as in
+// bgn_sum_batch_dev: one fixed-base product per output.
+namespace {
+int lincomb_check(const bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
+                  int w_bits, const uint8_t* r_be, size_t r_len, const uint8_t* out) {
+  if (!c) return fail(BGN_E_ARG, "null argument");
+  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
+  if (w_bits < 1 || w_bits > 31) return fail(BGN_E_ARG, "w_bits must be in [1, 31]");
+  if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
+  if (!nvec || !nrows) return BGN_OK;
+  if (!d) return fail(BGN_E_ARG, "d == 0");
+  if (!ct || !w || !out) return fail(BGN_E_ARG, "null argument");
+  if (d > kMaxBatch || nvec > kMaxBatch / d || nrows > kMaxBatch / d || nvec > kMaxBatch / nrows)
+    return fail(BGN_E_ARG, "batch too large (max 2^28 ciphertexts, weights and results per call)");
+  return BGN_OK;
+}
+}  // namespace
+
+int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
+                          int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out, void* stream) {
+  if (int rc = lincomb_check(c, nvec, nrows, d, level, ct, w, w_bits, r_be, r_len, out)) return rc;
+  if (!nvec || !nrows) return BGN_OK;
+  if ((uintptr_t)w & 3u) return fail(BGN_E_ARG, "w must be 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  const KernelTable* kt = c->kt;
+  if (!kt->lin_walk || !kt->sum_wire || (level == 2 && c->nl <= 40 && !c->d_barrett))
+    return fail(BGN_E_PARAM, "no linear-map kernel for these parameters");
+  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
+    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
+    if (rc) return rc;
+  }
+  const size_t ncols = nvec * d, nout = nvec * nrows, E = 2 * (size_t)c->L;
+  // a table entry: level 1 x, y, Z, prefix and a flag; level 2 re, im.  Half of what the context may still take goes to
+  // the tables, the rest to the other arrays of the call.
+  const size_t entry_bytes = level == 1 ? 4 * (size_t)c->nl * 4 + 1 : 2 * (size_t)c->nl * 4;
+  size_t avail = 0;
+  if (!ctx_free_memory(c, &avail, c->arena_bytes)) avail = 0;
+  const LinPlan plan = plan_lincomb(nvec, nrows, d, w_bits, avail / 2, entry_bytes, level, kSumChipLanes,
+                                    opt(c, &Options::lin_window), opt(c, &Options::lin_split));
+  const size_t nchunk = plan.nchunk, npart = nout * nchunk;
+  const int H = 1 << (plan.omega - 1);
+  SumPlan fold;
+  if (nchunk > 1) fold = plan_sum(nout, nchunk, level == 1 ? kSumChipLanes : 2 * kSumChipLanes, -1, level == 1 ? 4 : 2);
+  size_t cap[2] = {0, 0};              // elements of the two arrays of the fold's partials
+  for (int k = 0; k + 1 < fold.passes; ++k)
+    if (nout * fold.split[k] > cap[k & 1]) cap[k & 1] = nout * fold.split[k];
+  const size_t sc = round_up(ncols, 64), st = round_up(plan.entries ? plan.entries : 1, 64), sp = round_up(npart, 64),
+               so = round_up(nout, 64);
+  SoA2 A, T, W, O, T1, T2;
+  uint32_t *tz = nullptr, *tp = nullptr, *prefix = nullptr;
+  uint8_t *planes = nullptr, *pw = nullptr, *res = nullptr, *part[2] = {nullptr, nullptr};
+  if (int rc = carve(c, [&](Ws& ws) {
+    A = level == 1 ? ws.g1(sc) : ws.gt(sc);
+    planes = (uint8_t*)ws.cv.take((size_t)plan.nwin * d * nrows * (size_t)lin_digit_bytes(plan.omega));
+    if (plan.entries) {
+      T = level == 1 ? ws.g1(st) : ws.gt(st);
+      if (level == 1) { tz = ws.fp(st); tp = ws.fp(st); }
+    }
+    W = level == 1 ? ws.g1(sp) : ws.gt(sp);
+    if (nchunk > 1) pw = (uint8_t*)ws.cv.take(npart * E + 16);
+    for (int i = 0; i < 2; ++i)
+      if (cap[i]) part[i] = (uint8_t*)ws.cv.take(cap[i] * E + 16);
+    if (r_be) {
+      res = (uint8_t*)ws.cv.take(nout * E + 16);
+      if (level == 1) { O = ws.g1(so); T1 = ws.g1(so); T2 = ws.g1(so); prefix = ws.fp(so); }
+      else { O = ws.gt(so); T1 = ws.gt(so); T2 = ws.gt(so); }
+    }
+  })) return rc;
+  kt->decode(s, c->d_params, ct, c->L, ncols, A, nullptr, nullptr);
+  HIP_TRY(hipEventRecord(c->ev2, s));
+  LinDigitsArgs da;
+  da.w = w; da.nrows = nrows; da.d = d; da.w_bits = w_bits; da.omega = plan.omega; da.planes = planes;
+  kt->lin_digits(s, da);
+  if (plan.entries) {
+    LinTableArgs ta;
+    ta.cx = A.c0; ta.cy = A.c1; ta.cinf = A.inf; ta.sc = A.stride;
+    ta.tx = T.c0; ta.ty = T.c1; ta.tinf = T.inf; ta.st = T.stride;
+    ta.tz = tz; ta.tp = tp;
+    ta.ncols = ncols; ta.H = H;
+    kt->lin_table(s, c->d_params, c->d_consts, level, ta);
+  } else {
+    T = A;                             // window width 1: the entries are the elements themselves
+  }
+  HIP_TRY(hipEventRecord(c->ev3, s));
+  c->ev2_valid = true;
+  c->aux_kernel = !plan.entries ? "k_lin_digits" : level == 1 ? "k_lin_table_g1" : "k_lin_table_gt";
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  LinWalkArgs wa;
+  wa.tx = T.c0; wa.ty = T.c1; wa.tinf = T.inf; wa.st = T.stride; wa.H = H;
+  wa.planes = planes; wa.omega = plan.omega; wa.nwin = plan.nwin;
+  wa.ox = W.c0; wa.oy = W.c1; wa.oinf = W.inf; wa.so = W.stride;
+  wa.nvec = nvec; wa.nrows = nrows; wa.d = d; wa.nchunk = nchunk;
+  kt->lin_walk(s, c->d_params, c->d_consts, level, wa);
+  uint8_t* last = r_be ? res : out;
+  kt->encode(s, level == 1 ? W.inf : nullptr, W.c0, W.c1, W.stride, c->L, npart, nchunk > 1 ? pw : last);
+  const uint8_t* in = pw;
+  uint32_t len = (uint32_t)nchunk;
+  for (int k = 0; k < fold.passes; ++k) {
+    uint8_t* dst = k + 1 < fold.passes ? part[k & 1] : last;
+    kt->sum_wire(s, c->d_params, c->d_consts, c->d_barrett, level, in, c->L, nout, len, fold.split[k], dst);
+    in = dst;
+    len = fold.split[k];
+  }
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->last_kernel = level == 1 ? "k_lin_walk_g1" : "k_lin_walk_gt";
+  c->ev_valid = true;
+  if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
+    kt->decode_plain(s, c->d_params, res, c->L, nout, O);
+    if (level == 1) {
+      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, nout);
+      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, nout, out);
+    } else {
+      blind_l2(c, s, O, r_be, r_len, T1, T2, nout);
+      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, nout, out);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+
 int bgn_neg_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, uint8_t* out, void* stream) {
   if (!c || (count && (!a || !out))) return fail(BGN_E_ARG, "null argument");
   if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
@@ -2512,6 +2640,19 @@ int bgn_sum_batch(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const uint
   return host_call(c, 0, 0, {{ct, nullptr, seg_len * E, nseg}, {r_be, nullptr, r_len, nseg}, {nullptr, out, E, nseg}},
                    [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
                      return bgn_sum_batch_dev(c, nseg, seg_len, level, in[0], in[1], r_len, o[0], s);
+                   });
+}
+
+// The vectors, the weights and the results have rows of their own: no CombineOp, the _dev entry point is the device side.
+int bgn_lincomb_batch(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
+                      int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out) {
+  if (int rc = lincomb_check(c, nvec, nrows, d, level, ct, w, w_bits, r_be, r_len, out)) return rc;
+  if (!nvec || !nrows) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0, {{ct, nullptr, d * E, nvec}, {(const uint8_t*)w, nullptr, d * 4, nrows}, {r_be, nullptr, r_len, nvec * nrows},
+                             {nullptr, out, nrows * E, nvec}},
+                   [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_lincomb_batch_dev(c, nvec, nrows, d, level, in[0], (const int32_t*)in[1], w_bits, in[2], r_len, o[0], s);
                    });
 }
 

@@ -226,6 +226,30 @@ struct PolyLinArgs {
   int nbits;                                                                // scalar bits to scan (<= 8*klen)
 };
 
+// Linear maps of ciphertext vectors with plaintext weights (linops.hpp): out[v][r] = sum_j w[r][j] * ct[v][j].
+// Digit planes: w (nrows x d, row-major) -> signed digits of omega bits, window t of w[r][j] at element
+// (t*d + j)*nrows + r (int8; int16 at omega = 8, linrecode.hpp).
+struct LinDigitsArgs {
+  const int32_t* w; size_t nrows, d;
+  int w_bits, omega;
+  uint8_t* planes;
+};
+// Window tables: multiple (power) m = 1 .. H of column q < ncols at element q*H + (m-1).
+struct LinTableArgs {
+  const uint32_t* cx; const uint32_t* cy; const uint8_t* cinf; size_t sc;   // the decoded vector(s), canonical Montgomery
+  uint32_t* tx; uint32_t* ty; uint8_t* tinf; size_t st;                     // entries, canonical Montgomery (tinf: level 1)
+  uint32_t* tz; uint32_t* tp;                                               // level 1: one F_p of scratch per entry, each
+  size_t ncols; int H;
+};
+// The walk: lane (v*nchunk + c)*nrows + r sums the columns of chunk c for output (v, r) into element
+// (v*nrows + r)*nchunk + c of the output.  H == 1: the table is the decoded vector itself.
+struct LinWalkArgs {
+  const uint32_t* tx; const uint32_t* ty; const uint8_t* tinf; size_t st; int H;
+  const uint8_t* planes; int omega, nwin;
+  uint32_t* ox; uint32_t* oy; uint8_t* oinf; size_t so;                     // plain canonical out
+  size_t nvec, nrows, d, nchunk;
+};
+
 // The response of a proof of plaintext knowledge (proofs.hpp): dl[e] = (a[e] + c[e] * (v[e] + K * z[e])) mod n.
 // Unsigned big-endian rows; the lengths are at most n_len, the challenge rows 32 bytes; k is ONE scalar for the batch.
 struct PokArgs {
@@ -340,9 +364,13 @@ struct KernelTable {
   // not read beyond 40 limbs).  Either array at any byte address; they must not overlap.
   void (*sum_wire)(hipStream_t s, const void* params, const PairingConsts* consts, const void* barrett, int level,
                    const uint8_t* in, int L, size_t nseg, uint32_t len, uint32_t split, uint8_t* out);
+  // linear maps (linops.hpp): the digit planes of the weights, the window tables of the ciphertexts, the walk
+  void (*lin_digits)(hipStream_t s, LinDigitsArgs a);
+  void (*lin_table)(hipStream_t s, const void* params, const PairingConsts* consts, int level, LinTableArgs a);
+  void (*lin_walk)(hipStream_t s, const void* params, const PairingConsts* consts, int level, LinWalkArgs a);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
-  Entry entries[18];
+  Entry entries[22];
 };
 
 const KernelTable* kernel_table_nl3();

@@ -12,6 +12,7 @@
 #include "proofs.hpp"
 #include "randexp.hpp"
 #include "sumops.hpp"
+#include "linops.hpp"
 
 namespace bgn {
 
@@ -1157,6 +1158,68 @@ static void launch_poly_lin(hipStream_t s, const void* params, const PairingCons
                        consts, a);
 }
 
+// ---- linear maps of ciphertext vectors (linops.hpp) --------------------------------------------------------------
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_lin_digits(LinDigitsArgs A) {
+  const size_t i = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  if (i < A.nrows * A.d) lin_digits_lane(A, i);
+}
+
+template <int NL, int LEVEL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_lin_table(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, LinTableArgs A) {
+  __shared__ LFp<NL> L[4];
+  size_t q = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  if (!__ballot(q < A.ncols)) return;
+  if (q >= A.ncols) q = A.ncols - 1;         // a stand-in in the wave of the column's owner: identical writes in lockstep
+  if (LEVEL == 1)
+    lin_table_g1_lane<NL>(A, q, L, C, P);
+  else
+    lin_table_gt_lane<NL>(A, q, L, P);
+}
+
+template <int NL, int LEVEL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_lin_walk(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, LinWalkArgs A) {
+  __shared__ LFp<NL> L[4];
+  const size_t total = A.nvec * A.nchunk * A.nrows;
+  size_t lane = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  const bool live = lane < total;
+  if (!__ballot(live)) return;
+  if (!live) lane = total - 1;               // keep every index in range; nothing is taken or stored
+  if (LEVEL == 1)
+    lin_walk_g1_lane<NL>(A, lane, live, L, C, P);
+  else
+    lin_walk_gt_lane<NL>(A, lane, live, L, P);
+}
+
+static void launch_lin_digits(hipStream_t s, LinDigitsArgs a) {
+  if (!a.nrows || !a.d) return;
+  hipLaunchKernelGGL(k_lin_digits<NL_>, dim3(grid_for(a.nrows * a.d)), dim3(FP_BLOCK), 0, s, a);
+}
+
+static void launch_lin_table(hipStream_t s, const void* params, const PairingConsts* consts, int level, LinTableArgs a) {
+  if (!a.ncols || a.H < 2) return;
+  if (level == 1)
+    hipLaunchKernelGGL((k_lin_table<NL_, 1>), dim3(grid_for(a.ncols)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+  else
+    hipLaunchKernelGGL((k_lin_table<NL_, 2>), dim3(grid_for(a.ncols)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+}
+
+static void launch_lin_walk(hipStream_t s, const void* params, const PairingConsts* consts, int level, LinWalkArgs a) {
+  const size_t total = a.nvec * a.nchunk * a.nrows;
+  if (!total || !a.d) return;
+  if (level == 1)
+    hipLaunchKernelGGL((k_lin_walk<NL_, 1>), dim3(grid_for(total)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+  else
+    hipLaunchKernelGGL((k_lin_walk<NL_, 2>), dim3(grid_for(total)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+}
+
 template <int NL>
 __global__ void __launch_bounds__(FP_BLOCK)
 k_poly_split(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, PolySplitArgs A) {
@@ -1445,6 +1508,9 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
       launch_pok_response,
       launch_random_scalars,
       launch_sum_wire,
+      launch_lin_digits,
+      launch_lin_table,
+      launch_lin_walk,
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1466,6 +1532,10 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
 #else
        {"k_sum_gt_wire", (const void*)k_sum_acc_wire<NL_, 2>},
 #endif
+       {"k_lin_walk_g1", (const void*)k_lin_walk<NL_, 1>},
+       {"k_lin_walk_gt", (const void*)k_lin_walk<NL_, 2>},
+       {"k_lin_table_g1", (const void*)k_lin_table<NL_, 1>},
+       {"k_lin_table_gt", (const void*)k_lin_table<NL_, 2>},
        {nullptr, nullptr}},
   };
   return &t;

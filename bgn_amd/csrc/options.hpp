@@ -58,6 +58,10 @@ struct Options {
                            // level 2 — profiles/r10_sum_rates.csv; otherwise at least 2)
   V sum_lanes{0};          // ... and the lanes a planned pass wants busy (0: 65536 on level 1, one wave per SIMD; 131072 on
                            // level 2, whose pass runs two waves per SIMD)
+  V lin_window{-1};        // linear maps (bgn_lincomb_batch): window width of the weights' signed digits, 1 .. 8 (-1: planned,
+                           // dispatch.hpp plan_lincomb; narrowed until the tables fit the memory budget — same bytes)
+  V lin_split{-1};         // ... and the chunks the columns of one output are cut into (-1: planned; k >= 1: forced, clamped
+                           // to the number of columns — same bytes)
   V poly_karatsuba{1};     // Karatsuba levels on square MultPoly products
   V poly_levels{-1};       // forced number of levels (-1: planned)
   V poly_tables{-1};       // per-coefficient line tables: 0 never, 1 always, -1 by size
@@ -129,6 +133,8 @@ inline const OptionDesc* option_table(size_t* n) {
       {"sum_split", &Options::sum_split, true, nullptr},
       {"sum_run_min", &Options::sum_run_min, true, nullptr},
       {"sum_lanes", &Options::sum_lanes, true, nullptr},
+      {"lin_window", &Options::lin_window, true, nullptr},
+      {"lin_split", &Options::lin_split, true, nullptr},
       {"poly_karatsuba", &Options::poly_karatsuba, true, nullptr},
       {"poly_levels", &Options::poly_levels, true, nullptr},
       {"poly_tables", &Options::poly_tables, true, nullptr},

@@ -358,6 +358,30 @@ func (e *Engine) SumBatch(a []*Ciphertext, segLen int, l2 bool, r []*big.Int) ([
 	return e.unpack(out, l2), nil
 }
 
+// LinCombBatch applies one matrix of plaintext weights to nvec encrypted vectors of d ciphertexts each (a holds them
+// back to back): out[v*nrows+i] = sum_j w[i][j] * a[v*d+j], the loops of pk.MultConst (bgn.go:253-291) and pk.Add
+// (bgn.go:442-497) a weighted sum or a linear layer is computed with, as one call (bgn_lincomb_batch).  w is row-major,
+// nrows x d; a weight counts as sign(w) * (|w| mod 2^wBits) and a negative one subtracts.  r: one blinding scalar per
+// result in non-deterministic mode.
+func (e *Engine) LinCombBatch(a []*Ciphertext, w []int32, nrows, wBits int, l2 bool, r []*big.Int) ([]*Ciphertext, error) {
+	if nrows < 1 || len(w) == 0 || len(w)%nrows != 0 || len(a)%(len(w)/nrows) != 0 {
+		return nil, errors.New("bgn_amd: w must hold nrows rows of d weights and a whole vectors of d ciphertexts")
+	}
+	d := len(w) / nrows
+	nvec := len(a) / d
+	A := e.pack(a)
+	rb, rw := e.randomness(r)
+	out := make([]byte, nvec*nrows*2*e.L)
+	err := locked(func() C.int {
+		return C.bgn_lincomb_batch(e.h, C.size_t(nvec), C.size_t(nrows), C.size_t(d), levelOf(l2), u8(A),
+			(*C.int32_t)(unsafe.Pointer(&w[0])), C.int(wBits), u8(rb), C.size_t(rw), u8(out))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return e.unpack(out, l2), nil
+}
+
 // NegBatch is pk.Neg (bgn.go:436-438) in deterministic mode.
 func (e *Engine) NegBatch(a []*Ciphertext, l2 bool) ([]*Ciphertext, error) {
 	A := e.pack(a)
@@ -921,6 +945,44 @@ func (e *Engine) AddBatchDev(a, b *DeviceArray, r []*big.Int) (*DeviceArray, err
 // SubBatchDev is pk.Sub over device arrays (bgn.go:375-432; bgn_sub_batch_dev).
 func (e *Engine) SubBatchDev(a, b *DeviceArray, r []*big.Int) (*DeviceArray, error) {
 	return e.addSubDev(a, b, r, true)
+}
+
+// LinCombBatchDev is LinCombBatch over a device array of nvec*d elements (bgn_lincomb_batch_dev): the weights are
+// uploaded, the results stay on the device.
+func (e *Engine) LinCombBatchDev(a *DeviceArray, w []int32, nrows, wBits int, r []*big.Int) (*DeviceArray, error) {
+	if nrows < 1 || len(w) == 0 || len(w)%nrows != 0 || a.Count%(len(w)/nrows) != 0 {
+		return nil, errors.New("bgn_amd: w must hold nrows rows of d weights and a whole vectors of d ciphertexts")
+	}
+	d := len(w) / nrows
+	nvec := a.Count / d
+	dw, err := e.NewDeviceArray(len(w), 4, false)
+	if err != nil {
+		return nil, err
+	}
+	defer dw.Free()
+	err = locked(func() C.int { return C.bgn_dev_upload(e.h, dw.p, unsafe.Pointer(&w[0]), C.size_t(4*len(w))) })
+	if err != nil {
+		return nil, err
+	}
+	rb, rw := e.randomness(r)
+	dr, err := e.uploadScalars(rb, nvec*nrows, rw)
+	if err != nil {
+		return nil, err
+	}
+	defer dr.Free()
+	out, err := e.likeOut(nvec*nrows, a.L2)
+	if err != nil {
+		return nil, err
+	}
+	err = locked(func() C.int {
+		return C.bgn_lincomb_batch_dev(e.h, C.size_t(nvec), C.size_t(nrows), C.size_t(d), levelOf(a.L2), a.u8(),
+			(*C.int32_t)(dw.p), C.int(wBits), dr.ptrOrNil(), C.size_t(rw), out.u8(), nil)
+	})
+	if err != nil {
+		out.Free()
+		return nil, err
+	}
+	return out, nil
 }
 
 // SumBatchDev is SumBatch over a device array of nseg*segLen elements (bgn_sum_batch_dev): the sums stay on the device.

@@ -248,6 +248,31 @@ int bgn_neg_batch(bgn_ctx* ctx, size_t count, int level, const uint8_t* a, uint8
 int bgn_sum_batch(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
                   size_t r_len, uint8_t* out);
 
+/* Linear map of ciphertext vectors with plaintext weights: out[v][r] = sum_{j<d} w[r][j] * ct[v][j] for v < nvec,
+ * r < nrows — G1 addition and scalar multiples on level 1, F_p^2 products and powers on level 2.  ct: nvec*d elements,
+ * row-major; w: nrows*d signed 32-bit integers, row-major, host byte order, shared by all nvec vectors; out:
+ * nvec*nrows elements.  nvec == 1 is the matrix-vector product, nvec > 1 one model applied to many encrypted vectors.
+ * A weight is sign(w) * (|w| mod 2^w_bits), 1 <= w_bits <= 31: the caller states the magnitude bound, the engine never
+ * scans w on the host.  A negative weight means |w| * Neg(ct[j]) with Neg exactly as bgn_neg_batch computes it (level 1
+ * (x, p - y); level 2 (re, p - im), whatever the norm of the input); a zero weight contributes nothing; a row of zeros
+ * gives the identity (all zero bytes on level 1, 1 || 0 on level 2).  Blinded like bgn_sum_batch when r != NULL: one row
+ * of r_len bytes per OUTPUT, nvec*nrows rows, one fixed-base product per result.  The input contract is that of Add
+ * and Sum; the result is canonical wire bytes and does not depend on the order the engine accumulates in.  out must
+ * not overlap ct or w.  The device form takes ct and out at any byte address and needs w 4-byte aligned (BGN_E_ARG
+ * otherwise).  nvec == 0 or nrows == 0 is BGN_OK without work; BGN_E_ARG before any device work for a null context
+ * (refused first), d == 0, a bad level or w_bits, a null pointer, r with r_len == 0, or any of nvec*d, nvec*nrows,
+ * nrows*d above 2^28.  Neither form joins the combiner of concurrent small calls.
+ * The ciphertext vector is shared by all rows, so its work is done once: the weights are recoded on the device into
+ * signed digits of omega bits, every ciphertext gets a table of its multiples 1 .. 2^(omega-1) (one inversion per
+ * ciphertext on level 1), and one lane per output — per chunk of its columns when the outputs alone do not fill the
+ * chip, the chunks folded by the passes of bgn_sum_batch — walks the windows from the top with ONE table addition per
+ * (row, column, window) (csrc/linops.hpp; omega and the chunks planned by dispatch.hpp plan_lincomb inside the context's
+ * memory budget; options lin_window, lin_split — same bytes under every setting).
+ * Replaces the loops of MultConst (bgn.go:253-291) and Add (bgn.go:442-497) a weighted sum, a linear layer, EvalPoly or
+ * MultConstPoly is computed with. */
+int bgn_lincomb_batch(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
+                      int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out);
+
 /* out[i] = e(a[i], b[i]) (* e(Q,Q)^r[i] when r != NULL); inputs level 1, output level 2.
  * Replaces Mult (bgn.go:294-314). */
 int bgn_mult_batch(bgn_ctx* ctx, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be, size_t r_len,
@@ -369,6 +394,8 @@ int bgn_sub_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* a, c
 int bgn_neg_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* a, uint8_t* out, void* stream);
 int bgn_sum_batch_dev(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
                       size_t r_len, uint8_t* out, void* stream);
+int bgn_lincomb_batch_dev(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct,
+                          const int32_t* w, int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out, void* stream);
 int bgn_mult_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
                        size_t r_len, uint8_t* out, void* stream);
 int bgn_make_l2_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* a, uint8_t* out, void* stream);
@@ -541,7 +568,7 @@ double bgn_last_aux_kernel_ms(bgn_ctx* ctx);
 const char* bgn_last_aux_kernel_name(bgn_ctx* ctx);
 /* What the code object says about the kernel bgn_last_kernel_name names, when the engine knows its entry point
  * (the lane kernels: k_pairing<NL, 0|1>, k_g1_add_wire, k_gt_mul_wire, k_neg_wire, k_g1_add, k_gt_mul, k_g1_mul,
- * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response, k_random_scalars, k_sum_g1_wire, k_sum_gt_wire): out[0] = vector registers per lane, out[1] = scratch
+ * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response, k_random_scalars, k_sum_g1_wire, k_sum_gt_wire, k_lin_walk_g1, k_lin_walk_gt): out[0] = vector registers per lane, out[1] = scratch
  * (private-segment) bytes per lane, out[2] = static LDS bytes per workgroup, out[3] = threads per workgroup the
  * kernel may be launched with.  A kernel that is meant to hold everything in registers and has started to spill
  * shows here before it shows on a clock.  Returns BGN_E_ARG for a kernel it has no entry point of. */

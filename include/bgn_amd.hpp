@@ -468,6 +468,22 @@ class PublicKey {
     check(bgn_sum_batch(h_, nseg, seg_len, level, A.data(), r ? rb.data() : nullptr, rl, out.data()), "bgn_sum_batch");
     return split(out, level == 2);
   }
+  // Linear map (bgn_lincomb_batch): a holds nvec vectors of d ciphertexts, w nrows x d plaintext weights, row-major;
+  // result v*nrows + i is sum_j w[i][j] * a[v*d + j] — the loops of MultConst (bgn.go:253-291) and Add (bgn.go:442-497)
+  // over a shared vector.  A weight counts as sign(w) * (|w| mod 2^w_bits); r: one blinding scalar per result.
+  std::vector<Ciphertext> LinCombBatch(const std::vector<Ciphertext>& a, const std::vector<int32_t>& w, size_t nrows, int w_bits,
+                                       const std::vector<Scalar>* r = nullptr) const {
+    if (!nrows || w.empty() || w.size() % nrows || a.size() % (w.size() / nrows))
+      throw Error(BGN_E_ARG, "w must hold nrows rows of d weights and a whole vectors of d ciphertexts");
+    const size_t d = w.size() / nrows, nvec = a.size() / d;
+    const int level = a.empty() || !a[0].L2 ? 1 : 2;
+    size_t rl = 0;
+    Bytes A = join(a), rb, out(nvec * nrows * E_);
+    if (r) rb = pack(*r, rl);
+    check(bgn_lincomb_batch(h_, nvec, nrows, d, level, A.data(), w.data(), w_bits, r ? rb.data() : nullptr, rl, out.data()),
+          "bgn_lincomb_batch");
+    return split(out, level == 2);
+  }
   std::vector<Ciphertext> MultBatch(const std::vector<Ciphertext>& a, const std::vector<Ciphertext>& b,
                                     const std::vector<Scalar>* r = nullptr) const {
     size_t rl = 0;
