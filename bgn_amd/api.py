@@ -171,6 +171,21 @@ class Engine:
                                           rs.shape[1] if rs is not None else 0, _ptr(out)), "bgn_lincomb_batch")
         return out
 
+    def scan(self, level: int, ct: BytesLike, seg_len: int, r=None) -> np.ndarray:
+        """Prefix sums (bgn_scan_batch): `ct` holds nseg * seg_len elements row-major, row s*seg_len + i of the result
+        is the sum of the first i + 1 elements of segment s, blinded with one r per OUTPUT if given."""
+        A = _as_u8(ct, self.elem_bytes)
+        seg_len = int(seg_len)
+        if seg_len < 1 or len(A) % seg_len:
+            raise ValueError("the element count is not a multiple of seg_len")
+        rs = _scalars(r) if r is not None else None
+        if rs is not None and len(rs) != len(A):
+            raise ValueError("one blinding scalar per output is required")
+        out = self._out(len(A))
+        check(self._lib.bgn_scan_batch(self._h, len(A) // seg_len, seg_len, level, _ptr(A), _ptr(rs),
+                                       rs.shape[1] if rs is not None else 0, _ptr(out)), "bgn_scan_batch")
+        return out
+
     def mult(self, a: BytesLike, b: BytesLike, r=None) -> np.ndarray:
         A, B = _as_u8(a, self.elem_bytes), _as_u8(b, self.elem_bytes)
         if len(A) != len(B):
@@ -337,6 +352,16 @@ class Engine:
         check(self._lib.bgn_lincomb_batch_dev(self._h, nvec, nrows, d, level, ct.data_ptr(), w.data_ptr(), int(w_bits),
                                               r.data_ptr() if r is not None else None, r_len, out.data_ptr(),
                                               self._stream()), "bgn_lincomb_batch_dev")
+
+    def scan_dev(self, level: int, ct, out, nseg: int, seg_len: int, r=None, r_len: int = 0) -> None:
+        """Device-resident prefix sums (bgn_scan_batch_dev): ct and out hold nseg * seg_len elements; r (one row of r_len
+        big-endian bytes per output, on the device) blinds.  Arrays at any byte address; `out` must not overlap `ct`."""
+        self._need("ct", ct, nseg * seg_len * self.elem_bytes)
+        self._need("out", out, nseg * seg_len * self.elem_bytes)
+        self._need("r", r, nseg * seg_len * r_len)
+        check(self._lib.bgn_scan_batch_dev(self._h, nseg, seg_len, level, ct.data_ptr(),
+                                           r.data_ptr() if r is not None else None, r_len, out.data_ptr(),
+                                           self._stream()), "bgn_scan_batch_dev")
 
     def multconst_dev(self, level: int, a, k, k_len: int, out, count: Optional[int] = None, r=None, r_len: int = 0) -> None:
         """Device-resident MultConst (bgn.go:253-291): k holds count x k_len big-endian scalar bytes on the device;
@@ -976,6 +1001,25 @@ class PublicKey:
 
     def LinComb(self, weights: Sequence[int], cts: Sequence[Ciphertext]) -> Ciphertext:
         return self.LinCombBatch([list(weights)], cts)[0]
+
+    # -- prefix sums: the chain of Add a running total is computed with, as one engine call --
+    def ScanBatch(self, rows: Sequence[Sequence[Ciphertext]]) -> List[List[Ciphertext]]:
+        """The running sums of every row; the rows have one length and one level."""
+        rows = [list(r) for r in rows]
+        if not rows:
+            return []
+        seg_len = len(rows[0])
+        if seg_len == 0 or any(len(r) != seg_len for r in rows):
+            raise ValueError("ScanBatch needs rows of one non-zero length")
+        lvl = self._lvl(rows[0][0])
+        if any(self._lvl(c) != lvl for r in rows for c in r):
+            raise ValueError("ScanBatch needs operands of one level")
+        out = self.engine.scan(lvl, b"".join(c.C for r in rows for c in r), seg_len, self._r(len(rows) * seg_len))
+        cts = [Ciphertext(bytes(row), lvl == 2) for row in out]
+        return [cts[i:i + seg_len] for i in range(0, len(cts), seg_len)]
+
+    def Scan(self, cts: Sequence[Ciphertext]) -> List[Ciphertext]:
+        return self.ScanBatch([cts])[0]
 
     # -- MultConst: bgn.go:253-291 --
     def MultConst(self, c: Ciphertext, constant: int) -> Ciphertext:

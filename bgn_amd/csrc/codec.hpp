@@ -225,11 +225,11 @@ __device__ __forceinline__ void wire_to_limbs_stream(Fp<NL>& r, const u32* __res
 // L is the word's address (scalar arithmetic) and, for the last few dwords of each value, whether it exists
 // (wave-uniform).  With L odd an element has one half word besides: its last two bytes on even lanes, its first two
 // on odd ones.  No byte of a neighbouring lane is written.  StreamCodec<NL>::serves(L).
+// (limbs_to_wire_stream_at: the same for an element at byte B of the stage, B a multiple of 4 or, with L odd, 2 mod 4.)
 template <int NL>
-__device__ __forceinline__ void limbs_to_wire_stream(u32* __restrict__ w, u32 tid, int L, const Fp<NL>& x, const Fp<NL>& y) {
+__device__ __forceinline__ void limbs_to_wire_stream_at(u32* __restrict__ w, u32 B, int L, const Fp<NL>& x, const Fp<NL>& y) {
   constexpr int ND = StreamCodec<NL>::ND, FMIN = StreamCodec<NL>::FMIN;
   const int ws = L >> 2, bs = 8 * (L & 3);                // x starts ws dwords and bs bits up in V (wave-uniform)
-  const u32 B = tid * (u32)(2 * L);
   const u32 h = (0u - B) & 3u;
   const u32 sel = stream_sel(((u32)(2 * L) - h) & 3u);
   // word m pairs V's dwords i0 - m and i0 - m + 1; an element has i0 + 1 whole words (m = 0 .. i0)
@@ -284,6 +284,10 @@ __device__ __forceinline__ void limbs_to_wire_stream(u32* __restrict__ w, u32 ti
     uint16_t* w16 = (uint16_t*)w;
     w16[odd ? (B >> 1) : ((B + (u32)(2 * L) - 2u) >> 1)] = (uint16_t)half;
   }
+}
+template <int NL>
+__device__ __forceinline__ void limbs_to_wire_stream(u32* __restrict__ w, u32 tid, int L, const Fp<NL>& x, const Fp<NL>& y) {
+  limbs_to_wire_stream_at<NL>(w, tid * (u32)(2 * L), L, x, y);
 }
 
 // ---- LDS staging of a workgroup's slice of a wire array ---------------------------------------

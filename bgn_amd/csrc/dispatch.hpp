@@ -338,4 +338,52 @@ inline LinPlan plan_lincomb(size_t nvec, size_t nrows, size_t d, int w_bits, siz
   return p;
 }
 
+// Prefix sums (scanops.hpp): reduce, then scan.  Level k of the recursion scans nseg segments of len[k] elements in
+// chunks of c[k] (one lane per chunk; a segment's last chunk may be shorter): a launch leaves the chunk totals, level
+// k + 1 scans those — len[k+1] = ceil(len[k] / c[k]) per segment — and a second launch of level k applies them.  The
+// last level has one chunk per segment and needs no totals.  The choice of c:
+//   * a pass wants `chip_lanes` lanes busy: while the array is larger than that, c = ceil(len / ceil(chip_lanes / nseg));
+//   * a lane's run carries its one inversion (level 1) and the launches of the level below: c >= run_min, and c >= 2
+//     always, so that every level at least halves the length and the recursion ends;
+//   * the forward sweep of level 1 keeps four field elements per element of the lanes of one launch in the workspace,
+//     and the smallest launch is one workgroup: c <= max_chunk (0: no bound), which wins over run_min and the chip.
+// forced >= 1: c of the FIRST level, clamped like a planned one to [2, len] and to max_chunk; the levels below are
+// planned.  No byte of the result depends on any of this.
+struct ScanPlan {
+  int levels = 0;
+  uint32_t len[32] = {};
+  uint32_t c[32] = {};
+  uint32_t nch[32] = {};       // chunks per segment: ceil(len / c); 1 on the last level
+};
+
+inline ScanPlan plan_scan(size_t nseg, size_t seg_len, size_t chip_lanes, int64_t run_min, int64_t forced, size_t max_chunk) {
+  ScanPlan p;
+  if (!nseg || !seg_len) return p;
+  const size_t rmin = run_min < 2 ? 2 : (size_t)run_min;
+  if (!chip_lanes) chip_lanes = 1;
+  if (max_chunk == 1) max_chunk = 2;                                     // (the recursion has to shrink)
+  size_t len = seg_len;
+  for (;;) {
+    size_t c;
+    if (p.levels == 0 && forced >= 1) {
+      c = (size_t)forced;
+    } else {
+      const size_t by_chip = (chip_lanes + nseg - 1) / nseg;              // chunks per segment that fill the chip
+      c = (len + by_chip - 1) / by_chip;
+      if (c < rmin) c = rmin;
+    }
+    if (max_chunk && c > max_chunk) c = max_chunk;
+    if (c < 2) c = 2;
+    if (c > len) c = len;
+    const size_t nch = (len + c - 1) / c;
+    p.len[p.levels] = (uint32_t)len;
+    p.c[p.levels] = (uint32_t)c;
+    p.nch[p.levels] = (uint32_t)nch;
+    ++p.levels;
+    if (nch == 1) break;
+    len = nch;                                                           // (at most ceil(len / 2): 28 levels for 2^28)
+  }
+  return p;
+}
+
 }  // namespace bgn

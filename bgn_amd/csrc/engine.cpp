@@ -1891,6 +1891,134 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
   return BGN_OK;
 }
 
+// ---- prefix sums -----------------------------------------------------------------------------------------------
+// out[s*seg_len + i] = ct[s*seg_len] + ... + ct[s*seg_len + i]: reduce, then scan (scanops.hpp), planned by
+// dispatch.hpp plan_scan.  Level k of the plan leaves its chunk totals in the workspace, the level below scans them, and
+// level k's apply launch starts every chunk from the scanned total in front of it; the topmost apply writes `out`.
+// Blinded: it writes a workspace array instead, which takes one fixed-base product per OUTPUT through the path of the
+// blinded Add (blind_l1 / blind_l2) on its way to `out`.  The forward sweep of level 1 keeps four field elements per
+// element of the lanes of one launch; when the context's memory cannot hold a whole level, its lanes go in ranges —
+// any range is independent once the offsets exist.
+namespace {
+constexpr int64_t kScanRunMin = 4;          // shortest planned run: it carries a lane's inversion and the levels below
+
+struct ScanRun {
+  bgn_ctx* c;
+  hipStream_t s;
+  int level;
+  size_t nseg;
+  ScanPlan plan;
+  uint8_t* tot[32];                         // level k: the chunk totals, nseg x nch[k] wire elements
+  uint8_t* pre[32];                         // ... and their inclusive scan
+  uint32_t* jac;                            // the level-1 sweeps' workspace, `lanes` columns
+  size_t lanes;
+};
+
+// one launch of level k over all its lanes, in ranges of r.lanes
+void scan_launch(const ScanRun& r, int k, const uint8_t* in, const uint8_t* off, uint8_t* out, bool totals) {
+  ScanArgs a;
+  a.in = in; a.off = off; a.out = out;
+  a.L = r.c->L; a.totals = totals ? 1 : 0;
+  a.len = r.plan.len[k]; a.c = r.plan.c[k]; a.nch = r.plan.nch[k];
+  a.ws = r.jac; a.wstride = r.lanes;
+  const size_t nq = r.nseg * r.plan.nch[k];
+  const size_t step = r.level == 1 && !totals ? r.lanes : nq;
+  for (size_t q0 = 0; q0 < nq; q0 += step) {
+    a.q0 = q0;
+    a.q1 = nq - q0 < step ? nq : q0 + step;
+    r.c->kt->scan_wire(r.s, r.c->d_params, r.c->d_consts, r.c->d_barrett, r.level, a);
+  }
+}
+
+// the inclusive scan of nseg x plan.len[k] elements of `in` into `out`
+void scan_level(const ScanRun& r, int k, const uint8_t* in, uint8_t* out) {
+  if (r.plan.nch[k] == 1) {
+    scan_launch(r, k, in, nullptr, out, false);
+    return;
+  }
+  scan_launch(r, k, in, nullptr, r.tot[k], true);
+  scan_level(r, k + 1, r.tot[k], r.pre[k]);
+  scan_launch(r, k, in, r.pre[k], out, false);
+}
+}  // namespace
+
+int bgn_scan_batch_dev(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
+                       size_t r_len, uint8_t* out, void* stream) {
+  if (int rc = sum_check(c, nseg, seg_len, level, ct, r_be, r_len, out)) return rc;
+  if (!nseg) return BGN_OK;
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->kt->scan_wire || (level == 2 && c->nl <= 40 && !c->d_barrett))
+    return fail(BGN_E_PARAM, "no scan kernel for these parameters");
+  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
+    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
+    if (rc) return rc;
+  }
+  const size_t E = 2 * (size_t)c->L, count = nseg * seg_len;
+  const size_t block = (size_t)fp_block(c->nl);
+  // a quarter of what the context may still take goes to the sweeps' workspace: 16 * nl bytes per element of a launch,
+  // and a launch is at least one workgroup
+  const size_t per_elem = 4 * (size_t)c->nl * 4;
+  size_t avail = 0, max_chunk = 0;
+  if (level == 1) {
+    if (!ctx_free_memory(c, &avail, c->arena_bytes)) avail = 0;
+    max_chunk = avail / 4 / (per_elem * block);
+    if (max_chunk < 2) max_chunk = 2;
+  }
+  ScanRun run;
+  run.c = c; run.s = s; run.level = level; run.nseg = nseg; run.jac = nullptr; run.lanes = 0;
+  run.plan = plan_scan(nseg, seg_len, level == 1 ? kSumChipLanes : 2 * kSumChipLanes, kScanRunMin, opt(c, &Options::scan_chunk),
+                       max_chunk);
+  const ScanPlan& plan = run.plan;
+  size_t cmax = 0;
+  if (level == 1) {                    // columns of the workspace: every lane of the widest level, or what the quarter holds
+    for (int k = 0; k < plan.levels; ++k) {
+      if (plan.c[k] > cmax) cmax = plan.c[k];
+      if (round_up(nseg * plan.nch[k], block) > run.lanes) run.lanes = round_up(nseg * plan.nch[k], block);
+    }
+    const size_t fit = avail / 4 / (per_elem * cmax) / block * block;
+    if (run.lanes > fit) run.lanes = fit < block ? block : fit;
+    const int64_t range = opt(c, &Options::scan_range);
+    if (range >= 1 && run.lanes > round_up((size_t)range, block)) run.lanes = round_up((size_t)range, block);
+  }
+  const size_t st = round_up(count, 64);
+  uint8_t* res = nullptr;
+  SoA2 O, T1, T2;
+  uint32_t* prefix = nullptr;
+  if (int rc = carve(c, [&](Ws& w) {
+    for (int k = 0; k + 1 < plan.levels; ++k) {
+      run.tot[k] = (uint8_t*)w.cv.take(nseg * plan.nch[k] * E + 16);
+      run.pre[k] = (uint8_t*)w.cv.take(nseg * plan.nch[k] * E + 16);
+    }
+    if (level == 1) run.jac = (uint32_t*)w.cv.take(cmax * per_elem * run.lanes);
+    if (r_be) {
+      res = (uint8_t*)w.cv.take(count * E + 16);
+      if (level == 1) { O = w.g1(st); T1 = w.g1(st); T2 = w.g1(st); prefix = w.fp(st); }
+      else { O = w.gt(st); T1 = w.gt(st); T2 = w.gt(st); }
+    }
+  })) return rc;
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  scan_level(run, 0, ct, r_be ? res : out);
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->last_kernel = level == 1 ? "k_scan_g1_wire" : "k_scan_gt_wire";
+  c->ev_valid = true;
+  if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
+    const KernelTable* kt = c->kt;
+    kt->decode_plain(s, c->d_params, res, c->L, count, O);
+    if (level == 1) {
+      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, count);
+      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, count, out);
+    } else {
+      blind_l2(c, s, O, r_be, r_len, T1, T2, count);
+      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, count, out);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+
 int bgn_neg_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, uint8_t* out, void* stream) {
   if (!c || (count && (!a || !out))) return fail(BGN_E_ARG, "null argument");
   if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
@@ -2640,6 +2768,18 @@ int bgn_sum_batch(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const uint
   return host_call(c, 0, 0, {{ct, nullptr, seg_len * E, nseg}, {r_be, nullptr, r_len, nseg}, {nullptr, out, E, nseg}},
                    [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
                      return bgn_sum_batch_dev(c, nseg, seg_len, level, in[0], in[1], r_len, o[0], s);
+                   });
+}
+
+// One row of r per output, whole segments of ct and out: no CombineOp, the _dev entry point is the device side.
+int bgn_scan_batch(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be, size_t r_len,
+                   uint8_t* out) {
+  if (int rc = sum_check(c, nseg, seg_len, level, ct, r_be, r_len, out)) return rc;
+  if (!nseg) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0, {{ct, nullptr, seg_len * E, nseg}, {r_be, nullptr, seg_len * r_len, nseg}, {nullptr, out, seg_len * E, nseg}},
+                   [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_scan_batch_dev(c, nseg, seg_len, level, in[0], in[1], r_len, o[0], s);
                    });
 }
 

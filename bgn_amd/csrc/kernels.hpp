@@ -250,6 +250,22 @@ struct LinWalkArgs {
   size_t nvec, nrows, d, nchunk;
 };
 
+// Prefix sums (scanops.hpp).  One launch: lanes [q0, q1) of the nseg * nch chunk lanes.  totals != 0: write chunk q's
+// total to out[q] and nothing else (off unused); otherwise write every prefix to its element's place in `out`, starting from off[q - 1] (the
+// inclusive scan of the totals, nseg x nch) when `off` is given and the chunk is not its segment's first.
+// ws: the level-1 forward sweep's workspace, 4 * c elements of NL limbs per lane, limb stride wstride >= q1 - q0.
+struct ScanArgs {
+  const uint8_t* in;
+  const uint8_t* off;
+  uint8_t* out;
+  int L;
+  int totals;
+  uint32_t len, c, nch;
+  size_t q0, q1;
+  uint32_t* ws;
+  size_t wstride;
+};
+
 // The response of a proof of plaintext knowledge (proofs.hpp): dl[e] = (a[e] + c[e] * (v[e] + K * z[e])) mod n.
 // Unsigned big-endian rows; the lengths are at most n_len, the challenge rows 32 bytes; k is ONE scalar for the batch.
 struct PokArgs {
@@ -368,9 +384,14 @@ struct KernelTable {
   void (*lin_digits)(hipStream_t s, LinDigitsArgs a);
   void (*lin_table)(hipStream_t s, const void* params, const PairingConsts* consts, int level, LinTableArgs a);
   void (*lin_walk)(hipStream_t s, const void* params, const PairingConsts* consts, int level, LinWalkArgs a);
+  // one launch of a prefix sum, wire bytes to wire bytes (scanops.hpp): the chunk totals or the prefixes of the lanes
+  // [q0, q1); level 1 G1 sums, level 2 GT products (`barrett` as for gt_mul_wire, not read beyond 40 limbs).  Arrays at
+  // any byte address; `out` must not overlap `in` or `off`.
+  void (*scan_wire)(hipStream_t s, const void* params, const PairingConsts* consts, const void* barrett, int level,
+                    ScanArgs a);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
-  Entry entries[22];
+  Entry entries[24];
 };
 
 const KernelTable* kernel_table_nl3();

@@ -12,6 +12,7 @@
 #include "proofs.hpp"
 #include "randexp.hpp"
 #include "sumops.hpp"
+#include "scanops.hpp"
 #include "linops.hpp"
 
 namespace bgn {
@@ -799,6 +800,171 @@ static void launch_sum_wire(hipStream_t s, const void* params, const PairingCons
 #endif
 }
 
+// ---- prefix sums (scanops.hpp): the chunk totals or the prefixes, wire bytes to wire bytes ------------------------
+// One lane owns one chunk of a.c consecutive elements of its segment.  At step j the workgroup stages the FP_BLOCK
+// rows its lanes need — a chunk apart in HBM — through per-row slots of the stage (the table `tab` names the rows),
+// every lane takes its element, and in apply mode (a.totals == 0) puts prefix j back into the same slot, from where
+// the workgroup writes the rows out.  No __restrict__ on the arrays: the host applies the launches to its own totals.
+//
+// Level 2, up to 40 limbs: accumulator and element are four Fp in registers, the stage is the product's scratch — the
+// budget of k_gt_mul_wire (two waves per SIMD, two workgroups per CU).
+#if BGN_NL <= 40
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
+k_scan_gt_wire(const FpParams<NL>* __restrict__ P, const BarrettParams<NL>* __restrict__ Bp, ScanArgs a) {
+  constexpr int SWORDS = ScanStage<NL>::WORDS > NL * FP_BLOCK ? ScanStage<NL>::WORDS : NL * FP_BLOCK;
+  __shared__ alignas(16) u32 sw[SWORDS];
+  __shared__ u32 tab[FP_BLOCK];
+  const size_t EB = (size_t)(2 * a.L);
+  const u32 tid = threadIdx.x;
+  const u32 rsw = scan_row_words(EB);
+  const ScanLane ln = scan_lane(a.q0 + (size_t)blockIdx.x * FP_BLOCK + tid, a.q1, a.len, a.c, a.nch);
+  Fp<NL> acc0, acc1;
+  fp_zero(acc0);
+  fp_zero(acc1);
+  acc0.v[0] = 1;
+  const bool shifted = !a.totals && a.off != nullptr;     // workgroup-uniform
+  if (shifted) {
+    tab[tid] = ln.prev;
+    scan_stage_in(sw, rsw, tab, a.off, EB);
+    sum_decode<NL>(acc0, acc1, sw, scan_row_byte(tid, rsw, a.off, ln.prev == SCAN_NONE ? 0u : ln.prev, EB), a.L);
+    sum_gt_take<NL>(acc0, acc1, ln.prev != SCAN_NONE, P, Bp);
+  }
+#pragma unroll 1
+  for (u32 j = 0; j < a.c; ++j) {
+    const bool live = j < ln.n;
+    const u32 e = ln.e0 + j;
+    __syncthreads();                                      // the rows of the previous step are out: table and stage are free
+    tab[tid] = live ? e : SCAN_NONE;
+    scan_stage_in(sw, rsw, tab, a.in, EB);
+    Fp<NL> b0, b1;
+    sum_decode<NL>(b0, b1, sw, scan_row_byte(tid, rsw, a.in, live ? e : 0u, EB), a.L);   // idle lanes decode zeros: discarded
+    sum_gt_take<NL>(b0, b1, live, P, Bp);
+    __syncthreads();                                      // every lane has read its element: the stage is scratch now
+    if (j == 0 && !shifted) {
+      acc0 = b0;
+      acc1 = b1;
+    } else {
+      sum_gt_step<NL>(acc0, acc1, b0, b1, P, Bp, sw + tid, FP_BLOCK);
+    }
+    if (!a.totals) {
+      __syncthreads();                                    // ... and becomes the stage of the prefixes
+      if (live) scan_encode<NL>(sw, scan_row_byte(tid, rsw, a.out, e, EB), a.out, a.L, acc0, acc1);
+      scan_stage_out(sw, rsw, tab, a.out, EB);
+    }
+  }
+  if (a.totals) {
+    const u32 q = (u32)(a.q0 + (size_t)blockIdx.x * FP_BLOCK + tid);
+    __syncthreads();
+    tab[tid] = ln.n ? q : SCAN_NONE;
+    if (ln.n) scan_encode<NL>(sw, scan_row_byte(tid, rsw, a.out, q, EB), a.out, a.L, acc0, acc1);
+    scan_stage_out(sw, rsw, tab, a.out, EB);
+  }
+}
+#endif
+
+// Level 1 (LEVEL == 1: the two sweeps of scanops.hpp over a Jacobian accumulator) and, beyond 40 limbs, level 2
+// (LEVEL == 2: the Montgomery accumulator, converted per prefix).  LDS: the four slots of the accumulation; the stage
+// lies over the two scratch slots L[0], L[1], which nothing needs while rows are staged (barriers on both sides).
+template <int NL, int LEVEL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_scan_acc_wire(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, ScanArgs a) {
+  constexpr int LW = (int)(sizeof(LFp<NL>) / 4);
+  constexpr int FRONT = ScanStage<NL>::WORDS > 2 * LW ? ScanStage<NL>::WORDS : 2 * LW;
+  __shared__ alignas(16) u32 sw[FRONT + 2 * LW];
+  __shared__ u32 tab[FP_BLOCK];
+  LFp<NL>* Ls = reinterpret_cast<LFp<NL>*>(sw + (FRONT - 2 * LW));
+  const size_t EB = (size_t)(2 * a.L);
+  const u32 tid = threadIdx.x;
+  const u32 rsw = scan_row_words(EB);
+  const size_t lane = (size_t)blockIdx.x * FP_BLOCK + tid;          // its column of the workspace
+  const ScanLane ln = scan_lane(a.q0 + lane, a.q1, a.len, a.c, a.nch);
+  JacAcc<NL> S;                                           // LEVEL 2: X, Y are the accumulator's re, im
+  bool acc_inf = true;
+  if (LEVEL == 1) sum_g1_init<NL>(S, acc_inf, P);
+  else sum_gt_mont_init<NL>(S.X, S.Y, P);
+  if (!a.totals && a.off != nullptr) {                    // workgroup-uniform
+    tab[tid] = ln.prev;
+    scan_stage_in(sw, rsw, tab, a.off, EB);
+    Fp<NL> x, y;
+    sum_decode<NL>(x, y, sw, scan_row_byte(tid, rsw, a.off, ln.prev == SCAN_NONE ? 0u : ln.prev, EB), a.L);
+    __syncthreads();
+    if (LEVEL == 1) sum_g1_step<NL>(S, acc_inf, x, y, ln.prev != SCAN_NONE, Ls, P);
+    else sum_gt_mont_step<NL>(S.X, S.Y, x, y, ln.prev != SCAN_NONE, Ls, P);
+  }
+  const bool record = LEVEL == 1 && !a.totals;
+#pragma unroll 1
+  for (u32 j = 0; j < a.c; ++j) {
+    const bool live = j < ln.n;
+    const u32 e = ln.e0 + j;
+    __syncthreads();                                      // every lane is done with the scratch slots, the rows are out
+    tab[tid] = live ? e : SCAN_NONE;
+    scan_stage_in(sw, rsw, tab, a.in, EB);
+    Fp<NL> x, y;
+    sum_decode<NL>(x, y, sw, scan_row_byte(tid, rsw, a.in, live ? e : 0u, EB), a.L);
+    __syncthreads();                                      // every lane has read its element
+    if (LEVEL == 1) {
+      sum_g1_step<NL>(S, acc_inf, x, y, live, Ls, P);
+      if (record) scan_g1_record<NL>(S, acc_inf, live, a.ws, a.wstride, lane, j, Ls, P);
+    } else {
+      sum_gt_mont_step<NL>(S.X, S.Y, x, y, live, Ls, P);
+      if (!a.totals) {
+        sum_gt_mont_finish<NL>(x, y, S.X, S.Y, Ls, P);
+        __syncthreads();                                  // the scratch slots become the stage of the prefixes
+        if (live) scan_encode<NL>(sw, scan_row_byte(tid, rsw, a.out, e, EB), a.out, a.L, x, y);
+        scan_stage_out(sw, rsw, tab, a.out, EB);
+      }
+    }
+  }
+  if (record) {
+    {                                                     // one inversion for the lane's run: 1 / (Z_0 ... Z_(c-1))
+      Fp<NL> t, zi;
+      g_load<NL>(t, scan_ws_slot<NL>(a.ws, a.wstride, a.c - 1, 3), a.wstride, lane);
+      fp_inv<NL>(zi, t, Ls, C, P);                        // <1   (uses L0, L1)
+      a_store(S.T, zi);
+    }
+#pragma unroll 1
+    for (u32 j = a.c; j-- > 0;) {
+      const bool live = j < ln.n;
+      const u32 e = ln.e0 + j;
+      __syncthreads();                                    // the rows of the previous step are out
+      Fp<NL> x, y;
+      scan_g1_peel<NL>(x, y, S.T, S.U, a.ws, a.wstride, lane, j, Ls, P);
+      __syncthreads();                                    // the scratch slots become the stage of the prefixes
+      tab[tid] = live ? e : SCAN_NONE;
+      if (live) scan_encode<NL>(sw, scan_row_byte(tid, rsw, a.out, e, EB), a.out, a.L, x, y);
+      scan_stage_out(sw, rsw, tab, a.out, EB);
+    }
+  }
+  if (a.totals) {
+    Fp<NL> x, y;
+    if (LEVEL == 1) sum_g1_finish<NL>(x, y, S, acc_inf, Ls, C, P);
+    else sum_gt_mont_finish<NL>(x, y, S.X, S.Y, Ls, P);
+    const u32 q = (u32)(a.q0 + lane);
+    __syncthreads();
+    tab[tid] = ln.n ? q : SCAN_NONE;
+    if (ln.n) scan_encode<NL>(sw, scan_row_byte(tid, rsw, a.out, q, EB), a.out, a.L, x, y);
+    scan_stage_out(sw, rsw, tab, a.out, EB);
+  }
+}
+
+static void launch_scan_wire(hipStream_t s, const void* params, const PairingConsts* consts, const void* barrett, int level,
+                             ScanArgs a) {
+  if (a.q1 <= a.q0 || !a.len || !a.c || !a.nch) return;
+  const dim3 grid((unsigned)((a.q1 - a.q0 + FP_BLOCK - 1) / FP_BLOCK));
+  if (level == 1) {
+    hipLaunchKernelGGL((k_scan_acc_wire<NL_, 1>), grid, dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params, consts, a);
+    return;
+  }
+#if BGN_NL <= 40
+  hipLaunchKernelGGL(k_scan_gt_wire<NL_>, grid, dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                     (const BarrettParams<NL_>*)barrett, a);
+#else
+  (void)barrett;
+  hipLaunchKernelGGL((k_scan_acc_wire<NL_, 2>), grid, dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params, consts, a);
+#endif
+}
+
 template <int NL>
 __global__ void __launch_bounds__(FP_BLOCK)
 k_gt_pow(const FpParams<NL>* __restrict__ P, GtPowArgs A) {
@@ -1511,6 +1677,7 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
       launch_lin_digits,
       launch_lin_table,
       launch_lin_walk,
+      launch_scan_wire,
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1536,6 +1703,12 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
        {"k_lin_walk_gt", (const void*)k_lin_walk<NL_, 2>},
        {"k_lin_table_g1", (const void*)k_lin_table<NL_, 1>},
        {"k_lin_table_gt", (const void*)k_lin_table<NL_, 2>},
+       {"k_scan_g1_wire", (const void*)k_scan_acc_wire<NL_, 1>},
+#if BGN_NL <= 40
+       {"k_scan_gt_wire", (const void*)k_scan_gt_wire<NL_>},
+#else
+       {"k_scan_gt_wire", (const void*)k_scan_acc_wire<NL_, 2>},
+#endif
        {nullptr, nullptr}},
   };
   return &t;

@@ -58,6 +58,11 @@ struct Options {
                            // level 2 — profiles/r10_sum_rates.csv; otherwise at least 2)
   V sum_lanes{0};          // ... and the lanes a planned pass wants busy (0: 65536 on level 1, one wave per SIMD; 131072 on
                            // level 2, whose pass runs two waves per SIMD)
+  V scan_chunk{-1};        // prefix sums (bgn_scan_batch): elements per lane on the FIRST level of the recursion (-1: planned,
+                           // dispatch.hpp plan_scan; k >= 1: forced, clamped to [2, segment length] — same bytes)
+  V scan_range{0};         // ... and the lanes of one level-1 apply launch, whose forward sweep keeps 16 * limbs bytes per element in
+                           // the workspace (0: what a quarter of the context's free memory holds; k >= 1: at most k, in whole
+                           // workgroups — a level with more lanes runs in ranges; same bytes)
   V lin_window{-1};        // linear maps (bgn_lincomb_batch): window width of the weights' signed digits, 1 .. 8 (-1: planned,
                            // dispatch.hpp plan_lincomb; narrowed until the tables fit the memory budget — same bytes)
   V lin_split{-1};         // ... and the chunks the columns of one output are cut into (-1: planned; k >= 1: forced, clamped
@@ -133,6 +138,8 @@ inline const OptionDesc* option_table(size_t* n) {
       {"sum_split", &Options::sum_split, true, nullptr},
       {"sum_run_min", &Options::sum_run_min, true, nullptr},
       {"sum_lanes", &Options::sum_lanes, true, nullptr},
+      {"scan_chunk", &Options::scan_chunk, true, nullptr},
+      {"scan_range", &Options::scan_range, true, nullptr},
       {"lin_window", &Options::lin_window, true, nullptr},
       {"lin_split", &Options::lin_split, true, nullptr},
       {"poly_karatsuba", &Options::poly_karatsuba, true, nullptr},

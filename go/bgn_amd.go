@@ -382,6 +382,25 @@ func (e *Engine) LinCombBatch(a []*Ciphertext, w []int32, nrows, wBits int, l2 b
 	return e.unpack(out, l2), nil
 }
 
+// ScanBatch returns the running sums of every segment of segLen consecutive ciphertexts: out[s*segLen+i] is the sum
+// of the first i+1 elements of segment s — the chain of pk.Add (bgn.go:442-497) a running total is computed with, as
+// one call (bgn_scan_batch).  r: one blinding scalar per output in non-deterministic mode.
+func (e *Engine) ScanBatch(a []*Ciphertext, segLen int, l2 bool, r []*big.Int) ([]*Ciphertext, error) {
+	if segLen < 1 || len(a)%segLen != 0 {
+		return nil, errors.New("bgn_amd: the element count is not a multiple of segLen")
+	}
+	A := e.pack(a)
+	rb, rw := e.randomness(r)
+	out := make([]byte, len(a)*2*e.L)
+	err := locked(func() C.int {
+		return C.bgn_scan_batch(e.h, C.size_t(len(a)/segLen), C.size_t(segLen), levelOf(l2), u8(A), u8(rb), C.size_t(rw), u8(out))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return e.unpack(out, l2), nil
+}
+
 // NegBatch is pk.Neg (bgn.go:436-438) in deterministic mode.
 func (e *Engine) NegBatch(a []*Ciphertext, l2 bool) ([]*Ciphertext, error) {
 	A := e.pack(a)
@@ -1003,6 +1022,31 @@ func (e *Engine) SumBatchDev(a *DeviceArray, segLen int, r []*big.Int) (*DeviceA
 	}
 	err = locked(func() C.int {
 		return C.bgn_sum_batch_dev(e.h, C.size_t(nseg), C.size_t(segLen), levelOf(a.L2), a.u8(), dr.ptrOrNil(), C.size_t(rw), out.u8(), nil)
+	})
+	if err != nil {
+		out.Free()
+		return nil, err
+	}
+	return out, nil
+}
+
+// ScanBatchDev is ScanBatch over a device array of nseg*segLen elements (bgn_scan_batch_dev): the prefixes stay on the device.
+func (e *Engine) ScanBatchDev(a *DeviceArray, segLen int, r []*big.Int) (*DeviceArray, error) {
+	if segLen < 1 || a.Count%segLen != 0 {
+		return nil, errors.New("bgn_amd: the element count is not a multiple of segLen")
+	}
+	rb, rw := e.randomness(r)
+	dr, err := e.uploadScalars(rb, a.Count, rw)
+	if err != nil {
+		return nil, err
+	}
+	defer dr.Free()
+	out, err := e.likeOut(a.Count, a.L2)
+	if err != nil {
+		return nil, err
+	}
+	err = locked(func() C.int {
+		return C.bgn_scan_batch_dev(e.h, C.size_t(a.Count/segLen), C.size_t(segLen), levelOf(a.L2), a.u8(), dr.ptrOrNil(), C.size_t(rw), out.u8(), nil)
 	})
 	if err != nil {
 		out.Free()

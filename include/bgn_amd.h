@@ -273,6 +273,27 @@ int bgn_sum_batch(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const ui
 int bgn_lincomb_batch(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
                       int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out);
 
+/* Prefix sums: out[s*seg_len + i] = ct[s*seg_len] + ... + ct[s*seg_len + i] for s < nseg, i < seg_len — the inclusive
+ * scan of every segment, G1 addition on level 1, the F_p^2 product on level 2 — each output blinded with Q^r[.] resp.
+ * e(Q,Q)^r[.] when r != NULL (one row of r_len bytes per OUTPUT, nseg*seg_len rows).  A running sum, a cumulative
+ * histogram, every sliding-window total (W[i] = S[i+w-1] - S[i-1]: two offset views and one bgn_sub_batch_dev) and
+ * ragged group-by totals (two gathered prefixes and a subtraction) come from it.
+ * ct and out: nseg*seg_len elements, row-major; out must not overlap ct.  nseg == 0 is BGN_OK; seg_len == 0 or
+ * nseg*seg_len above 2^28 is BGN_E_ARG; seg_len == 1 copies (and blinds).  The input contract and the canonical output
+ * are those of bgn_sum_batch: level 1 takes valid points or the identity (all zero, in and out), level 2 reduces
+ * residues >= p first and its identity is 1 || 0.  Every prefix is the canonical wire form of a group element, so no
+ * byte depends on how the engine cuts the work: reduce, then scan — a lane owns a chunk of consecutive elements, the
+ * chunk totals are scanned by the same kernels one level down, and the apply launch starts every chunk from the
+ * scanned total in front of it; level 1 pays ONE inversion per lane and run, not one per output (option scan_chunk;
+ * csrc/scanops.hpp).  O(1) group operations per element, against log2(seg_len) full-size Adds for the doubling scheme
+ * over offset views.  The device form takes arrays at any byte address.  Neither form joins the combiner of
+ * concurrent small calls.  2^20 device-resident elements of a 1024-bit key against the doubling scheme on the same
+ * data: 1 x 2^20 level 1 in 21.6 ms (28.3 ms), level 2 in 4.35 ms (8.30 ms); 4096 x 256: 9.87 (11.7) and 2.21 (4.14) ms;
+ * 65536 x 16: 4.03 (6.46) and 1.33 (2.51) ms (profiles/r12_scan_rates.csv).
+ * Replaces the chain of Add (bgn.go:442-497) a running total is computed with. */
+int bgn_scan_batch(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
+                   size_t r_len, uint8_t* out);
+
 /* out[i] = e(a[i], b[i]) (* e(Q,Q)^r[i] when r != NULL); inputs level 1, output level 2.
  * Replaces Mult (bgn.go:294-314). */
 int bgn_mult_batch(bgn_ctx* ctx, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be, size_t r_len,
@@ -396,6 +417,8 @@ int bgn_sum_batch_dev(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, cons
                       size_t r_len, uint8_t* out, void* stream);
 int bgn_lincomb_batch_dev(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct,
                           const int32_t* w, int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out, void* stream);
+int bgn_scan_batch_dev(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
+                       size_t r_len, uint8_t* out, void* stream);
 int bgn_mult_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,
                        size_t r_len, uint8_t* out, void* stream);
 int bgn_make_l2_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* a, uint8_t* out, void* stream);

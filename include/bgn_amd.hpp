@@ -484,6 +484,17 @@ class PublicKey {
           "bgn_lincomb_batch");
     return split(out, level == 2);
   }
+  // Prefix sums (bgn_scan_batch): the running sums of every segment of seg_len consecutive elements — the chain of
+  // Add (bgn.go:442-497) a running total is computed with; r: one blinding scalar per output.
+  std::vector<Ciphertext> ScanBatch(const std::vector<Ciphertext>& a, size_t seg_len, const std::vector<Scalar>* r = nullptr) const {
+    if (!seg_len || a.size() % seg_len) throw Error(BGN_E_ARG, "the element count is not a multiple of seg_len");
+    const int level = a.empty() || !a[0].L2 ? 1 : 2;
+    size_t rl = 0;
+    Bytes A = join(a), rb, out(a.size() * E_);
+    if (r) rb = pack(*r, rl);
+    check(bgn_scan_batch(h_, a.size() / seg_len, seg_len, level, A.data(), r ? rb.data() : nullptr, rl, out.data()), "bgn_scan_batch");
+    return split(out, level == 2);
+  }
   std::vector<Ciphertext> MultBatch(const std::vector<Ciphertext>& a, const std::vector<Ciphertext>& b,
                                     const std::vector<Scalar>* r = nullptr) const {
     size_t rl = 0;
@@ -569,6 +580,16 @@ class PublicKey {
     if (r) dr = scalars_dev(*r, rl);
     check(bgn_sum_batch_dev(h_, nseg, seg_len, a.L2 ? 2 : 1, a.data(), r ? dr.data() : nullptr, rl, out.data(), nullptr),
           "bgn_sum_batch_dev");
+    return out;
+  }
+  // bgn_scan_batch_dev over a device array of nseg * seg_len elements: as many prefixes, left on the device.
+  DeviceArray ScanBatchDev(const DeviceArray& a, size_t seg_len, const std::vector<Scalar>* r = nullptr) const {
+    if (!seg_len || a.Count % seg_len) throw Error(BGN_E_ARG, "the element count is not a multiple of seg_len");
+    size_t rl = 0;
+    DeviceArray dr, out(h_, a.Count, E_, a.L2);
+    if (r) dr = scalars_dev(*r, rl);
+    check(bgn_scan_batch_dev(h_, a.Count / seg_len, seg_len, a.L2 ? 2 : 1, a.data(), r ? dr.data() : nullptr, rl, out.data(), nullptr),
+          "bgn_scan_batch_dev");
     return out;
   }
   DeviceArray NegBatchDev(const DeviceArray& a) const {
