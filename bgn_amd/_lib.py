@@ -43,6 +43,8 @@ PROTOTYPES = {
     "bgn_neg_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p]),
     "bgn_sum_batch": (C.c_int, [_ctx, _sz, _sz, C.c_int, _u8p, _u8p, _sz, _u8p]),
     "bgn_lincomb_batch": (C.c_int, [_ctx, _sz, _sz, _sz, C.c_int, _u8p, _u8p, C.c_int, _u8p, _sz, _u8p]),
+    "bgn_sparse_lincomb_batch": (C.c_int, [_ctx, _sz, _sz, _sz, _sz, _sz, C.c_int, _u8p, _u8p, _u8p, _u8p, C.c_int, _u8p, _sz,
+                                           _u8p]),
     "bgn_scan_batch": (C.c_int, [_ctx, _sz, _sz, C.c_int, _u8p, _u8p, _sz, _u8p]),
     "bgn_mult_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _sz, _u8p]),
     "bgn_make_l2_batch": (C.c_int, [_ctx, _sz, _u8p, _u8p]),
@@ -72,6 +74,8 @@ PROTOTYPES = {
     "bgn_neg_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, C.c_void_p]),
     "bgn_sum_batch_dev": (C.c_int, [_ctx, _sz, _sz, C.c_int, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_lincomb_batch_dev": (C.c_int, [_ctx, _sz, _sz, _sz, C.c_int, _u8p, _u8p, C.c_int, _u8p, _sz, _u8p, C.c_void_p]),
+    "bgn_sparse_lincomb_batch_dev": (C.c_int, [_ctx, _sz, _sz, _sz, _sz, _sz, C.c_int, _u8p, _u8p, _u8p, _u8p, C.c_int, _u8p,
+                                               _sz, _u8p, C.c_void_p]),
     "bgn_scan_batch_dev": (C.c_int, [_ctx, _sz, _sz, C.c_int, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_mult_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_make_l2_batch_dev": (C.c_int, [_ctx, _sz, _u8p, _u8p, C.c_void_p]),

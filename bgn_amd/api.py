@@ -171,6 +171,41 @@ class Engine:
                                           rs.shape[1] if rs is not None else 0, _ptr(out)), "bgn_lincomb_batch")
         return out
 
+    def sparse_lincomb(self, level: int, ct: BytesLike, row_ptr, col, w, d: Optional[int] = None, w_bits: Optional[int] = None,
+                       row_max: Optional[int] = None, r=None, nvec: int = 1) -> np.ndarray:
+        """Sparse linear map (bgn_sparse_lincomb_batch): `ct` holds nvec vectors of d elements; (row_ptr, col, w) is a
+        compressed-row structure of nrows = len(row_ptr) - 1 rows; row v*nrows + i of the result is the sum of
+        w[e] * ct[v][col[e]] over the entries e of row i, blinded with one r per result if given.  d defaults to
+        len(ct) / nvec, w_bits to the bit length of the largest |w|, row_max to the longest row of a well-formed
+        row_ptr.  Indices outside the stated bounds follow the rules of include/bgn_amd.h: they contribute nothing."""
+        A = _as_u8(ct, self.elem_bytes)
+        rp = np.ascontiguousarray(np.asarray(row_ptr, dtype=np.int64).astype(np.uint32))
+        cl = np.ascontiguousarray(np.asarray(col, dtype=np.int64).astype(np.uint32))
+        wa = np.asarray(w, dtype=np.int64)
+        if rp.ndim != 1 or len(rp) < 1 or cl.ndim != 1 or wa.shape != cl.shape:
+            raise ValueError("row_ptr must hold nrows + 1 entries, col and w one entry per nonzero")
+        nrows, nnz, nvec = len(rp) - 1, len(cl), int(nvec)
+        if d is None:
+            d = len(A) // nvec if nvec > 0 else 0
+        if d < 1 or nvec < 0 or len(A) != nvec * d:
+            raise ValueError("ct must hold nvec vectors of d elements")
+        top = int(np.abs(wa).max()) if nnz else 0
+        if top > 0x7FFFFFFF:
+            raise ValueError("weights must fit 31 bits and a sign")
+        if w_bits is None:
+            w_bits = max(1, top.bit_length())
+        if row_max is None:
+            row_max = max(1, int(np.diff(rp.astype(np.int64)).max())) if nrows else 1
+        wa = np.ascontiguousarray(wa, dtype=np.int32)
+        rs = _scalars(r) if r is not None else None
+        if rs is not None and len(rs) != nvec * nrows:
+            raise ValueError("one blinding scalar per result is required")
+        out = self._out(nvec * nrows)
+        check(self._lib.bgn_sparse_lincomb_batch(self._h, nvec, nrows, d, nnz, int(row_max), level, _ptr(A), _ptr(rp),
+                                                 _ptr(cl) if nnz else None, _ptr(wa) if nnz else None, int(w_bits), _ptr(rs),
+                                                 rs.shape[1] if rs is not None else 0, _ptr(out)), "bgn_sparse_lincomb_batch")
+        return out
+
     def scan(self, level: int, ct: BytesLike, seg_len: int, r=None) -> np.ndarray:
         """Prefix sums (bgn_scan_batch): `ct` holds nseg * seg_len elements row-major, row s*seg_len + i of the result
         is the sum of the first i + 1 elements of segment s, blinded with one r per OUTPUT if given."""
@@ -352,6 +387,24 @@ class Engine:
         check(self._lib.bgn_lincomb_batch_dev(self._h, nvec, nrows, d, level, ct.data_ptr(), w.data_ptr(), int(w_bits),
                                               r.data_ptr() if r is not None else None, r_len, out.data_ptr(),
                                               self._stream()), "bgn_lincomb_batch_dev")
+
+    def sparse_lincomb_dev(self, level: int, ct, row_ptr, col, w, w_bits: int, out, nvec: int, nrows: int, d: int, nnz: int,
+                           row_max: int, r=None, r_len: int = 0) -> None:
+        """Device-resident sparse linear map (bgn_sparse_lincomb_batch_dev): ct holds nvec * d elements, row_ptr
+        nrows + 1 uint32, col nnz uint32 and w nnz int32 (all three 4-byte aligned), out nvec * nrows elements; r (nvec *
+        nrows x r_len big-endian bytes on the device) blinds each result.  Stream-ordered, nothing is read back: indices
+        outside nnz / d / row_max contribute nothing.  ct and out at any byte address; `out` must not overlap an input."""
+        self._need("ct", ct, nvec * d * self.elem_bytes)
+        self._need("row_ptr", row_ptr, (nrows + 1) * 4)
+        self._need("col", col, nnz * 4)
+        self._need("w", w, nnz * 4)
+        self._need("out", out, nvec * nrows * self.elem_bytes)
+        self._need("r", r, nvec * nrows * r_len)
+        check(self._lib.bgn_sparse_lincomb_batch_dev(self._h, nvec, nrows, d, nnz, row_max, level, ct.data_ptr(),
+                                                     row_ptr.data_ptr(), col.data_ptr() if nnz else None,
+                                                     w.data_ptr() if nnz else None, int(w_bits),
+                                                     r.data_ptr() if r is not None else None, r_len, out.data_ptr(),
+                                                     self._stream()), "bgn_sparse_lincomb_batch_dev")
 
     def scan_dev(self, level: int, ct, out, nseg: int, seg_len: int, r=None, r_len: int = 0) -> None:
         """Device-resident prefix sums (bgn_scan_batch_dev): ct and out hold nseg * seg_len elements; r (one row of r_len
@@ -1001,6 +1054,22 @@ class PublicKey:
 
     def LinComb(self, weights: Sequence[int], cts: Sequence[Ciphertext]) -> Ciphertext:
         return self.LinCombBatch([list(weights)], cts)[0]
+
+    def SparseLinCombBatch(self, row_ptr, col, w, cts: Sequence[Ciphertext]) -> List[Ciphertext]:
+        """out[i] = sum over the entries e of row i of w[e] * cts[col[e]] for a compressed-row structure (row_ptr,
+        col, w) over the len(cts) columns; one level.  A column outside the vector is refused here."""
+        cts = list(cts)
+        if not cts:
+            raise ValueError("SparseLinCombBatch needs at least one ciphertext")
+        rp, cl = np.asarray(row_ptr, dtype=np.int64), np.asarray(col, dtype=np.int64)
+        if rp.ndim != 1 or len(rp) < 1 or rp[0] != 0 or rp[-1] != len(cl) or (np.diff(rp) < 0).any() or \
+                ((cl < 0) | (cl >= len(cts))).any():
+            raise ValueError("SparseLinCombBatch needs a well-formed row_ptr and columns inside the vector")
+        lvl = self._lvl(cts[0])
+        if any(self._lvl(c) != lvl for c in cts):
+            raise ValueError("SparseLinCombBatch needs operands of one level")
+        out = self.engine.sparse_lincomb(lvl, b"".join(c.C for c in cts), rp, cl, w, r=self._r(len(rp) - 1))
+        return [Ciphertext(bytes(row), lvl == 2) for row in out]
 
     # -- prefix sums: the chain of Add a running total is computed with, as one engine call --
     def ScanBatch(self, rows: Sequence[Sequence[Ciphertext]]) -> List[List[Ciphertext]]:

@@ -338,6 +338,79 @@ inline LinPlan plan_lincomb(size_t nvec, size_t nrows, size_t d, int w_bits, siz
   return p;
 }
 
+// Sparse linear maps (sparseops.hpp): out[v][r] = sum_{e in row r} w[e] * ct[v][col[e]], nnz entries in rows of at most
+// row_max.  The planner counts nonzeros, not nrows * d, and never sees the index arrays: a lane's run is taken at its
+// bound rm = min(row_max, nnz) (a wave costs its longest row anyway).  The constants are those of plan_lincomb.
+//   nchunk  the chunks a row's entries are cut into evenly, one lane each, folded by the passes of plan_sum: as many as
+//           fill `chip_lanes` lanes while a chunk keeps kLinMinRun entries; and at least ceil(rm / kSpMaxRun), so that no
+//           wave carries a run of more than kSpMaxRun additions per window while the rest of the chip idles (at that
+//           length the lane's own doublings and conversion are below a hundredth of its run).  1 <= nchunk <= rm.
+//   omega   a lane costs nwin * (9 omega + 13 ceil(rm / nchunk)) + 40 (level 2: 2, 3, 2), the tables nvec*d * (H-1)
+//           steps within `budget_bytes` and 2^28 entries.  A table pays only when several rows read a column: with
+//           nnz <= d no column is shared on average and the planned window is 1 (the decoded vector is the table).
+// Known limit: rows are cut evenly and a wave costs its longest row, so one giant row among short ones wastes lanes —
+// every row gets nchunk lanes, most of them empty.  Splitting by entries across row boundaries is not done.
+// forced_window in 1 .. 8 and forced_split >= 1 override (the window narrowed until its table fits; the split clamped
+// to rm and to 2^28 partials).
+constexpr size_t kSpMaxRun = 1024;
+
+inline LinPlan plan_sparse_lincomb(size_t nvec, size_t nrows, size_t d, size_t nnz, size_t row_max, int w_bits,
+                                   size_t budget_bytes, size_t entry_bytes, int level, size_t chip_lanes,
+                                   int64_t forced_window, int64_t forced_split) {
+  LinPlan p;
+  if (!nvec || !nrows || !d || w_bits < 1 || w_bits > 31) return p;
+  if (!chip_lanes) chip_lanes = 1;
+  const size_t ncols = nvec * d, nout = nvec * nrows;
+  const size_t rm = row_max < nnz ? row_max : nnz;
+  // chunks
+  size_t nchunk = 1;
+  if (forced_split >= 1) {
+    nchunk = (size_t)forced_split;
+  } else {
+    if (nout < chip_lanes) {
+      const size_t by_chip = (chip_lanes + nout - 1) / nout, by_run = rm / kLinMinRun;
+      nchunk = by_run < by_chip ? by_run : by_chip;
+    }
+    const size_t by_wave = (rm + kSpMaxRun - 1) / kSpMaxRun;
+    if (nchunk < by_wave) nchunk = by_wave;
+  }
+  if (nchunk > rm) nchunk = rm;
+  if (nchunk > kMaxBatch / nout) nchunk = kMaxBatch / nout;
+  if (nchunk < 1) nchunk = 1;
+  p.nchunk = nchunk;
+  // window
+  const LinCost k = lin_cost(level);
+  const auto fits = [&](int omega) {
+    const size_t e = lin_table_entries(ncols, omega);
+    return omega == 1 || (e <= kMaxBatch && entry_bytes <= budget_bytes && e <= budget_bytes / entry_bytes);
+  };
+  const auto rounds = [&](size_t lanes) { return (double)((lanes + chip_lanes - 1) / chip_lanes); };
+  int best = 1;
+  if (forced_window >= 1) {
+    best = forced_window > kLinPlanMaxWindow ? kLinPlanMaxWindow : (int)forced_window;
+    while (!fits(best)) --best;
+  } else if (nnz > d) {
+    double best_cost = 0;
+    const double run = (double)((rm + nchunk - 1) / nchunk);
+    for (int omega = 1; omega <= kLinPlanMaxWindow; ++omega) {
+      if (!fits(omega)) break;
+      const int nwin = lin_plan_windows(w_bits, omega);
+      const double H = (double)((size_t)1 << (omega - 1));
+      const double table = omega > 1 ? rounds(ncols) * (H - 1) * k.c_table : 0;
+      const double walk = rounds(nout * nchunk) * (nwin * (omega * k.c_dbl + run * k.c_add) + k.c_fin);
+      const double cost = table + walk;
+      if (omega == 1 || cost < best_cost) {
+        best = omega;
+        best_cost = cost;
+      }
+    }
+  }
+  p.omega = best;
+  p.nwin = lin_plan_windows(w_bits, best);
+  p.entries = lin_table_entries(ncols, best);
+  return p;
+}
+
 // Prefix sums (scanops.hpp): reduce, then scan.  Level k of the recursion scans nseg segments of len[k] elements in
 // chunks of c[k] (one lane per chunk; a segment's last chunk may be shorter): a launch leaves the chunk totals, level
 // k + 1 scans those — len[k+1] = ceil(len[k] / c[k]) per segment — and a second launch of level k applies them.  The

@@ -1891,6 +1891,142 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
   return BGN_OK;
 }
 
+// ---- sparse linear maps ------------------------------------------------------------------------------------------
+// out[v][r] = sum_{e in row r} w[e] * ct[v][col[e]] over a compressed-row structure (sparseops.hpp), planned by
+// dispatch.hpp plan_sparse_lincomb from nnz and row_max: the vectors are decoded once, the entries' weights recoded into
+// entry-major digit planes, the window tables of the dense map built per ciphertext (none at window width 1) and the
+// rows' entries walked by one lane per (output, chunk of the row).  Encoding, the fold of the chunks and the blinding are
+// those of bgn_lincomb_batch_dev.  Nothing is read back: the index arrays are only ever seen by the kernels, which clip
+// them to the stated bounds.
+namespace {
+int sparse_lincomb_check(const bgn_ctx* c, size_t nvec, size_t nrows, size_t d, size_t nnz, size_t row_max, int level,
+                         const uint8_t* ct, const uint32_t* row_ptr, const uint32_t* col, const int32_t* w, int w_bits,
+                         const uint8_t* r_be, size_t r_len, const uint8_t* out) {
+  if (!c) return fail(BGN_E_ARG, "null argument");
+  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
+  if (w_bits < 1 || w_bits > 31) return fail(BGN_E_ARG, "w_bits must be in [1, 31]");
+  if (r_be && !r_len) return fail(BGN_E_ARG, "r_len == 0");
+  if (!nvec || !nrows) return BGN_OK;
+  if (!d) return fail(BGN_E_ARG, "d == 0");
+  if (nnz && !row_max) return fail(BGN_E_ARG, "row_max == 0");
+  if (!ct || !row_ptr || !out || (nnz && (!col || !w))) return fail(BGN_E_ARG, "null argument");
+  const size_t rm = row_max < nnz ? row_max : nnz;
+  if (d > kMaxBatch || nvec > kMaxBatch / d || nvec > kMaxBatch / nrows || nnz > kMaxBatch || (rm && nrows > kMaxBatch / rm))
+    return fail(BGN_E_ARG, "batch too large (max 2^28 ciphertexts, entries, results and row slots per call)");
+  return BGN_OK;
+}
+}  // namespace
+
+int bgn_sparse_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, size_t nnz, size_t row_max, int level,
+                                 const uint8_t* ct, const uint32_t* row_ptr, const uint32_t* col, const int32_t* w,
+                                 int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out, void* stream) {
+  if (int rc = sparse_lincomb_check(c, nvec, nrows, d, nnz, row_max, level, ct, row_ptr, col, w, w_bits, r_be, r_len, out))
+    return rc;
+  if (!nvec || !nrows) return BGN_OK;
+  if (((uintptr_t)row_ptr | (uintptr_t)col | (uintptr_t)w) & 3u)
+    return fail(BGN_E_ARG, "row_ptr, col and w must be 4-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  const KernelTable* kt = c->kt;
+  if (!kt->sp_walk || !kt->lin_table || !kt->sum_wire || (level == 2 && c->nl <= 40 && !c->d_barrett))
+    return fail(BGN_E_PARAM, "no sparse linear-map kernel for these parameters");
+  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
+    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
+    if (rc) return rc;
+  }
+  const size_t ncols = nvec * d, nout = nvec * nrows, E = 2 * (size_t)c->L;
+  const size_t entry_bytes = level == 1 ? 4 * (size_t)c->nl * 4 + 1 : 2 * (size_t)c->nl * 4;      // as for the dense map
+  size_t avail = 0;
+  if (!ctx_free_memory(c, &avail, c->arena_bytes)) avail = 0;
+  const size_t chip = level == 1 ? kSumChipLanes : 2 * kSumChipLanes;
+  const LinPlan plan = plan_sparse_lincomb(nvec, nrows, d, nnz, row_max, w_bits, avail / 2, entry_bytes, level, chip,
+                                           opt(c, &Options::lin_window), opt(c, &Options::lin_split));
+  const size_t nchunk = plan.nchunk, npart = nout * nchunk;
+  const int H = 1 << (plan.omega - 1);
+  SumPlan fold;
+  if (nchunk > 1) fold = plan_sum(nout, nchunk, chip, -1, level == 1 ? 4 : 2);
+  size_t cap[2] = {0, 0};              // elements of the two arrays of the fold's partials
+  for (int k = 0; k + 1 < fold.passes; ++k)
+    if (nout * fold.split[k] > cap[k & 1]) cap[k & 1] = nout * fold.split[k];
+  const size_t sc = round_up(ncols, 64), st = round_up(plan.entries ? plan.entries : 1, 64), sp = round_up(npart, 64),
+               so = round_up(nout, 64), nnz_pad = round_up(nnz ? nnz : 1, 64);
+  SoA2 A, T, W, O, T1, T2;
+  uint32_t *tz = nullptr, *tp = nullptr, *prefix = nullptr;
+  uint8_t *planes = nullptr, *pw = nullptr, *res = nullptr, *part[2] = {nullptr, nullptr};
+  if (int rc = carve(c, [&](Ws& ws) {
+    A = level == 1 ? ws.g1(sc) : ws.gt(sc);
+    planes = (uint8_t*)ws.cv.take((size_t)plan.nwin * nnz_pad * (size_t)lin_digit_bytes(plan.omega));
+    if (plan.entries) {
+      T = level == 1 ? ws.g1(st) : ws.gt(st);
+      if (level == 1) { tz = ws.fp(st); tp = ws.fp(st); }
+    }
+    W = level == 1 ? ws.g1(sp) : ws.gt(sp);
+    if (nchunk > 1) pw = (uint8_t*)ws.cv.take(npart * E + 16);
+    for (int i = 0; i < 2; ++i)
+      if (cap[i]) part[i] = (uint8_t*)ws.cv.take(cap[i] * E + 16);
+    if (r_be) {
+      res = (uint8_t*)ws.cv.take(nout * E + 16);
+      if (level == 1) { O = ws.g1(so); T1 = ws.g1(so); T2 = ws.g1(so); prefix = ws.fp(so); }
+      else { O = ws.gt(so); T1 = ws.gt(so); T2 = ws.gt(so); }
+    }
+  })) return rc;
+  kt->decode(s, c->d_params, ct, c->L, ncols, A, nullptr, nullptr);
+  HIP_TRY(hipEventRecord(c->ev2, s));
+  SpDigitsArgs da;
+  da.w = w; da.col = col; da.nnz = nnz; da.nnz_pad = nnz_pad; da.d = d; da.w_bits = w_bits; da.omega = plan.omega;
+  da.planes = planes;
+  kt->sp_digits(s, da);
+  if (plan.entries) {
+    LinTableArgs ta;
+    ta.cx = A.c0; ta.cy = A.c1; ta.cinf = A.inf; ta.sc = A.stride;
+    ta.tx = T.c0; ta.ty = T.c1; ta.tinf = T.inf; ta.st = T.stride;
+    ta.tz = tz; ta.tp = tp;
+    ta.ncols = ncols; ta.H = H;
+    kt->lin_table(s, c->d_params, c->d_consts, level, ta);
+  } else {
+    T = A;                             // window width 1: the entries are the elements themselves
+  }
+  HIP_TRY(hipEventRecord(c->ev3, s));
+  c->ev2_valid = true;
+  c->aux_kernel = !plan.entries ? "k_sp_digits" : level == 1 ? "k_lin_table_g1" : "k_lin_table_gt";
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  SpWalkArgs wa;
+  wa.tx = T.c0; wa.ty = T.c1; wa.tinf = T.inf; wa.st = T.stride; wa.H = H;
+  wa.planes = planes; wa.nnz_pad = nnz_pad; wa.omega = plan.omega; wa.nwin = plan.nwin;
+  wa.row_ptr = row_ptr; wa.col = col;
+  wa.ox = W.c0; wa.oy = W.c1; wa.oinf = W.inf; wa.so = W.stride;
+  wa.nvec = nvec; wa.nrows = nrows; wa.d = d; wa.nnz = nnz; wa.nchunk = nchunk;
+  wa.row_max = (uint32_t)(row_max < kMaxBatch ? row_max : kMaxBatch);       // (a row has at most nnz <= 2^28 entries)
+  kt->sp_walk(s, c->d_params, c->d_consts, level, wa);
+  uint8_t* last = r_be ? res : out;
+  kt->encode(s, level == 1 ? W.inf : nullptr, W.c0, W.c1, W.stride, c->L, npart, nchunk > 1 ? pw : last);
+  const uint8_t* in = pw;
+  uint32_t len = (uint32_t)nchunk;
+  for (int k = 0; k < fold.passes; ++k) {
+    uint8_t* dst = k + 1 < fold.passes ? part[k & 1] : last;
+    kt->sum_wire(s, c->d_params, c->d_consts, c->d_barrett, level, in, c->L, nout, len, fold.split[k], dst);
+    in = dst;
+    len = fold.split[k];
+  }
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->last_kernel = level == 1 ? "k_sp_walk_g1" : "k_sp_walk_gt";
+  c->ev_valid = true;
+  if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
+    kt->decode_plain(s, c->d_params, res, c->L, nout, O);
+    if (level == 1) {
+      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, nout);
+      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, nout, out);
+    } else {
+      blind_l2(c, s, O, r_be, r_len, T1, T2, nout);
+      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, nout, out);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+
 // ---- prefix sums -----------------------------------------------------------------------------------------------
 // out[s*seg_len + i] = ct[s*seg_len] + ... + ct[s*seg_len + i]: reduce, then scan (scanops.hpp), planned by
 // dispatch.hpp plan_scan.  Level k of the plan leaves its chunk totals in the workspace, the level below scans them, and
@@ -2793,6 +2929,23 @@ int bgn_lincomb_batch(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int level
                              {nullptr, out, nrows * E, nvec}},
                    [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
                      return bgn_lincomb_batch_dev(c, nvec, nrows, d, level, in[0], (const int32_t*)in[1], w_bits, in[2], r_len, o[0], s);
+                   });
+}
+
+// The vectors, the index arrays and the results have rows of their own: no CombineOp, the _dev entry point is the device side.
+int bgn_sparse_lincomb_batch(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, size_t nnz, size_t row_max, int level,
+                             const uint8_t* ct, const uint32_t* row_ptr, const uint32_t* col, const int32_t* w, int w_bits,
+                             const uint8_t* r_be, size_t r_len, uint8_t* out) {
+  if (int rc = sparse_lincomb_check(c, nvec, nrows, d, nnz, row_max, level, ct, row_ptr, col, w, w_bits, r_be, r_len, out))
+    return rc;
+  if (!nvec || !nrows) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L;
+  return host_call(c, 0, 0, {{ct, nullptr, d * E, nvec}, {row_ptr, nullptr, 4, nrows + 1}, {col, nullptr, 4, nnz}, {w, nullptr, 4, nnz},
+                             {r_be, nullptr, r_len, nvec * nrows}, {nullptr, out, nrows * E, nvec}},
+                   [&](size_t, uint8_t* const* in, uint8_t* const* o, hipStream_t s) {
+                     return bgn_sparse_lincomb_batch_dev(c, nvec, nrows, d, nnz, row_max, level, in[0], (const uint32_t*)in[1],
+                                                         (const uint32_t*)in[2], (const int32_t*)in[3], w_bits, in[4], r_len,
+                                                         o[0], s);
                    });
 }
 

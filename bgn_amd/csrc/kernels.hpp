@@ -250,6 +250,24 @@ struct LinWalkArgs {
   size_t nvec, nrows, d, nchunk;
 };
 
+// Sparse linear maps (sparseops.hpp): out[v][r] = sum_{e in row r} w[e] * ct[v][col[e]] over a compressed-row structure.
+// Digit planes: window t of w[e] at element t*nnz_pad + e (int8; int16 at omega = 8); zero where col[e] >= d.
+struct SpDigitsArgs {
+  const int32_t* w; const uint32_t* col; size_t nnz, nnz_pad, d;
+  int w_bits, omega;
+  uint8_t* planes;
+};
+// The walk: workgroup (v*nchunk + c, block of FP_BLOCK rows); the lane of row r sums chunk c's share of the row into
+// element (v*nrows + r)*nchunk + c of the output.  The tables are those of LinTableArgs.
+struct SpWalkArgs {
+  const uint32_t* tx; const uint32_t* ty; const uint8_t* tinf; size_t st; int H;
+  const uint8_t* planes; size_t nnz_pad; int omega, nwin;
+  const uint32_t* row_ptr; const uint32_t* col;                             // nrows + 1 and nnz words
+  uint32_t* ox; uint32_t* oy; uint8_t* oinf; size_t so;                     // plain canonical out
+  size_t nvec, nrows, d, nnz, nchunk;
+  uint32_t row_max;
+};
+
 // Prefix sums (scanops.hpp).  One launch: lanes [q0, q1) of the nseg * nch chunk lanes.  totals != 0: write chunk q's
 // total to out[q] and nothing else (off unused); otherwise write every prefix to its element's place in `out`, starting from off[q - 1] (the
 // inclusive scan of the totals, nseg x nch) when `off` is given and the chunk is not its segment's first.
@@ -389,9 +407,12 @@ struct KernelTable {
   // any byte address; `out` must not overlap `in` or `off`.
   void (*scan_wire)(hipStream_t s, const void* params, const PairingConsts* consts, const void* barrett, int level,
                     ScanArgs a);
+  // sparse linear maps (sparseops.hpp): the digit planes of the entries' weights and the walk over the rows' entries
+  void (*sp_digits)(hipStream_t s, SpDigitsArgs a);
+  void (*sp_walk)(hipStream_t s, const void* params, const PairingConsts* consts, int level, SpWalkArgs a);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
-  Entry entries[24];
+  Entry entries[28];
 };
 
 const KernelTable* kernel_table_nl3();

@@ -14,6 +14,7 @@
 #include "sumops.hpp"
 #include "scanops.hpp"
 #include "linops.hpp"
+#include "sparseops.hpp"
 
 namespace bgn {
 
@@ -1386,6 +1387,51 @@ static void launch_lin_walk(hipStream_t s, const void* params, const PairingCons
                        consts, a);
 }
 
+// ---- sparse linear maps (sparseops.hpp) --------------------------------------------------------------------------
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_sp_digits(SpDigitsArgs A) {
+  const size_t e = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  if (e < A.nnz) sp_digits_lane(A, e);
+}
+
+// Workgroup b = (v*nchunk + c) * nblk + (block of FP_BLOCK rows), nblk = ceil(nrows / FP_BLOCK).
+template <int NL, int LEVEL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_sp_walk(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, SpWalkArgs A) {
+  __shared__ LFp<NL> L[4];
+  __shared__ u32 rp[FP_BLOCK + 1];
+  const size_t nblk = (A.nrows + FP_BLOCK - 1) / FP_BLOCK;
+  const size_t vc = (size_t)blockIdx.x / nblk;
+  const size_t r0 = ((size_t)blockIdx.x - vc * nblk) * FP_BLOCK;
+  for (u32 i = threadIdx.x; i <= (u32)FP_BLOCK; i += FP_BLOCK) rp[i] = r0 + i <= A.nrows ? A.row_ptr[r0 + i] : 0;
+  __syncthreads();
+  const size_t r = r0 + threadIdx.x;
+  const bool live = r < A.nrows;
+  if (!__ballot(live)) return;
+  const SpLane ln = sp_lane(A, vc, r, live, rp);
+  if (LEVEL == 1)
+    sp_walk_g1_lane<NL>(A, ln, live, L, C, P);
+  else
+    sp_walk_gt_lane<NL>(A, ln, live, L, P);
+}
+
+static void launch_sp_digits(hipStream_t s, SpDigitsArgs a) {
+  if (!a.nnz) return;
+  hipLaunchKernelGGL(k_sp_digits<NL_>, dim3(grid_for(a.nnz)), dim3(FP_BLOCK), 0, s, a);
+}
+
+static void launch_sp_walk(hipStream_t s, const void* params, const PairingConsts* consts, int level, SpWalkArgs a) {
+  if (!a.nvec || !a.nrows || !a.nchunk) return;
+  const size_t blocks = a.nvec * a.nchunk * (size_t)grid_for(a.nrows);      // <= 2^28 lanes in all: fits a grid
+  if (level == 1)
+    hipLaunchKernelGGL((k_sp_walk<NL_, 1>), dim3((unsigned)blocks), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+  else
+    hipLaunchKernelGGL((k_sp_walk<NL_, 2>), dim3((unsigned)blocks), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+}
+
 template <int NL>
 __global__ void __launch_bounds__(FP_BLOCK)
 k_poly_split(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, PolySplitArgs A) {
@@ -1678,6 +1724,8 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
       launch_lin_table,
       launch_lin_walk,
       launch_scan_wire,
+      launch_sp_digits,
+      launch_sp_walk,
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1709,6 +1757,8 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
 #else
        {"k_scan_gt_wire", (const void*)k_scan_acc_wire<NL_, 2>},
 #endif
+       {"k_sp_walk_g1", (const void*)k_sp_walk<NL_, 1>},
+       {"k_sp_walk_gt", (const void*)k_sp_walk<NL_, 2>},
        {nullptr, nullptr}},
   };
   return &t;

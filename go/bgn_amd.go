@@ -382,6 +382,46 @@ func (e *Engine) LinCombBatch(a []*Ciphertext, w []int32, nrows, wBits int, l2 b
 	return e.unpack(out, l2), nil
 }
 
+// u32p and i32p pass an index or weight slice to C; nil for an empty one (nnz == 0 takes no col and no w).
+func u32p(v []uint32) *C.uint32_t {
+	if len(v) == 0 {
+		return nil
+	}
+	return (*C.uint32_t)(unsafe.Pointer(&v[0]))
+}
+
+func i32p(v []int32) *C.int32_t {
+	if len(v) == 0 {
+		return nil
+	}
+	return (*C.int32_t)(unsafe.Pointer(&v[0]))
+}
+
+// SparseLinCombBatch applies one sparse matrix of plaintext weights, in compressed-row form, to nvec encrypted vectors
+// of d ciphertexts each (a holds them back to back): out[v*nrows+i] is the sum of w[e] * a[v*d+col[e]] over the entries
+// rowPtr[i] .. rowPtr[i+1]-1 of row i, nrows = len(rowPtr)-1 — a window over a series, a banded operator, a weighted
+// group-by (bgn_sparse_lincomb_batch).  rowMax bounds the rows' lengths; entries past it, entry indices past len(col)
+// and columns past d contribute nothing.  A weight counts as sign(w) * (|w| mod 2^wBits).  r: one blinding scalar per
+// result in non-deterministic mode.
+func (e *Engine) SparseLinCombBatch(a []*Ciphertext, d int, rowPtr, col []uint32, w []int32, rowMax, wBits int, l2 bool, r []*big.Int) ([]*Ciphertext, error) {
+	if d < 1 || len(rowPtr) < 1 || len(col) != len(w) || len(a)%d != 0 || rowMax < 0 {
+		return nil, errors.New("bgn_amd: rowPtr must hold nrows+1 entries, col and w one per nonzero, a whole vectors of d ciphertexts")
+	}
+	nrows := len(rowPtr) - 1
+	nvec := len(a) / d
+	A := e.pack(a)
+	rb, rw := e.randomness(r)
+	out := make([]byte, nvec*nrows*2*e.L)
+	err := locked(func() C.int {
+		return C.bgn_sparse_lincomb_batch(e.h, C.size_t(nvec), C.size_t(nrows), C.size_t(d), C.size_t(len(col)), C.size_t(rowMax),
+			levelOf(l2), u8(A), u32p(rowPtr), u32p(col), i32p(w), C.int(wBits), u8(rb), C.size_t(rw), u8(out))
+	})
+	if err != nil {
+		return nil, err
+	}
+	return e.unpack(out, l2), nil
+}
+
 // ScanBatch returns the running sums of every segment of segLen consecutive ciphertexts: out[s*segLen+i] is the sum
 // of the first i+1 elements of segment s — the chain of pk.Add (bgn.go:442-497) a running total is computed with, as
 // one call (bgn_scan_batch).  r: one blinding scalar per output in non-deterministic mode.
@@ -996,6 +1036,55 @@ func (e *Engine) LinCombBatchDev(a *DeviceArray, w []int32, nrows, wBits int, r 
 	err = locked(func() C.int {
 		return C.bgn_lincomb_batch_dev(e.h, C.size_t(nvec), C.size_t(nrows), C.size_t(d), levelOf(a.L2), a.u8(),
 			(*C.int32_t)(dw.p), C.int(wBits), dr.ptrOrNil(), C.size_t(rw), out.u8(), nil)
+	})
+	if err != nil {
+		out.Free()
+		return nil, err
+	}
+	return out, nil
+}
+
+// SparseLinCombBatchDev is SparseLinCombBatch over a device array of nvec*d elements (bgn_sparse_lincomb_batch_dev): the
+// three index arrays are uploaded into one device array (rowPtr, col, w back to back, each 4-byte aligned), the results
+// stay on the device.
+func (e *Engine) SparseLinCombBatchDev(a *DeviceArray, d int, rowPtr, col []uint32, w []int32, rowMax, wBits int, r []*big.Int) (*DeviceArray, error) {
+	if d < 1 || len(rowPtr) < 1 || len(col) != len(w) || a.Count%d != 0 || rowMax < 0 {
+		return nil, errors.New("bgn_amd: rowPtr must hold nrows+1 entries, col and w one per nonzero, a whole vectors of d ciphertexts")
+	}
+	nrows := len(rowPtr) - 1
+	nvec := a.Count / d
+	nnz := len(col)
+	idx := make([]uint32, 0, len(rowPtr)+2*nnz)
+	idx = append(idx, rowPtr...)
+	idx = append(idx, col...)
+	for _, v := range w {
+		idx = append(idx, uint32(v))
+	}
+	di, err := e.NewDeviceArray(len(idx), 4, false)
+	if err != nil {
+		return nil, err
+	}
+	defer di.Free()
+	err = locked(func() C.int { return C.bgn_dev_upload(e.h, di.p, unsafe.Pointer(&idx[0]), C.size_t(4*len(idx))) })
+	if err != nil {
+		return nil, err
+	}
+	rb, rw := e.randomness(r)
+	dr, err := e.uploadScalars(rb, nvec*nrows, rw)
+	if err != nil {
+		return nil, err
+	}
+	defer dr.Free()
+	out, err := e.likeOut(nvec*nrows, a.L2)
+	if err != nil {
+		return nil, err
+	}
+	err = locked(func() C.int {
+		base := (*C.uint32_t)(di.p)
+		dcol := (*C.uint32_t)(unsafe.Add(di.p, 4*len(rowPtr)))
+		dw := (*C.int32_t)(unsafe.Add(di.p, 4*(len(rowPtr)+nnz)))
+		return C.bgn_sparse_lincomb_batch_dev(e.h, C.size_t(nvec), C.size_t(nrows), C.size_t(d), C.size_t(nnz), C.size_t(rowMax),
+			levelOf(a.L2), a.u8(), base, dcol, dw, C.int(wBits), dr.ptrOrNil(), C.size_t(rw), out.u8(), nil)
 	})
 	if err != nil {
 		out.Free()

@@ -273,7 +273,34 @@ int bgn_sum_batch(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const ui
 int bgn_lincomb_batch(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
                       int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out);
 
-/* Prefix sums: out[s*seg_len + i] = ct[s*seg_len] + ... + ct[s*seg_len + i] for s < nseg, i < seg_len — the inclusive
+/* Sparse linear map of ciphertext vectors: out[v][r] = sum_{e in row r} w[e] * ct[v][col[e]] for v < nvec, r < nrows —
+ * a window or FIR filter over an encrypted series, a banded operator, a weighted group-by with plaintext keys, an
+ * aggregation over neighbour lists — where the dense call would walk nrows*d weights, most of them zero.  The index
+ * arrays are a compressed-row structure shared by all nvec vectors of d ciphertexts: row_ptr has nrows + 1 entries,
+ * col and w have nnz (host byte order).  Weights, w_bits, Neg, zero weights, the identity of an empty sum, blinding (one
+ * row of r per OUTPUT), the input contract and the canonical output are those of bgn_lincomb_batch; the same column may
+ * appear several times in a row.
+ * The engine never scans the index arrays on the host (the device form is stream-ordered, nothing is read back), so the
+ * caller states their bounds and indices outside them have defined meanings: row r is the entries row_ptr[r] ..
+ * row_ptr[r] + len - 1 with len = min(row_ptr[r+1] - row_ptr[r], row_max) when row_ptr[r+1] > row_ptr[r] and 0
+ * otherwise (entries past row_max are dropped); an entry index >= nnz or a col[e] >= d contributes nothing.  No address
+ * is formed from an index that was not checked first.
+ * nvec == 0 or nrows == 0 is BGN_OK without work; nnz == 0 writes identities (blinded if r; col and w may be NULL).
+ * BGN_E_ARG before any device work for a null context (refused first), a bad level or w_bits, r with r_len == 0,
+ * d == 0, row_max == 0 with nnz > 0, a null pointer, or any of nvec*d, nvec*nrows, nnz, nrows*min(row_max, nnz) above
+ * 2^28; the device form also for row_ptr, col or w not 4-byte aligned (ct and out at any byte address).  out must not
+ * overlap any input.  Neither form joins the combiner of concurrent small calls.
+ * One thread per entry recodes its weight into signed digits, entry-major; the tables of multiples are those of the
+ * dense map, built only when columns are shared (nnz > d); a workgroup walks 256 consecutive rows of one vector, its
+ * row bounds read once into LDS, every wave to its longest row; long rows are cut evenly into chunks folded by the
+ * passes of bgn_sum_batch (csrc/sparseops.hpp; planned by dispatch.hpp plan_sparse_lincomb from nnz and row_max;
+ * options lin_window and lin_split = chunks per row — same bytes under every setting).  Rows are cut evenly and a wave
+ * costs its longest row: one giant row among short ones wastes lanes. */
+int bgn_sparse_lincomb_batch(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, size_t nnz, size_t row_max, int level,
+                             const uint8_t* ct, const uint32_t* row_ptr, const uint32_t* col, const int32_t* w,
+                             int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out);
+
+/* Prefix sums: out[s*seg_len + i] = ct[s*seg_len] + ...+ ct[s*seg_len + i] for s < nseg, i < seg_len — the inclusive
  * scan of every segment, G1 addition on level 1, the F_p^2 product on level 2 — each output blinded with Q^r[.] resp.
  * e(Q,Q)^r[.] when r != NULL (one row of r_len bytes per OUTPUT, nseg*seg_len rows).  A running sum, a cumulative
  * histogram, every sliding-window total (W[i] = S[i+w-1] - S[i-1]: two offset views and one bgn_sub_batch_dev) and
@@ -417,6 +444,9 @@ int bgn_sum_batch_dev(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, cons
                       size_t r_len, uint8_t* out, void* stream);
 int bgn_lincomb_batch_dev(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct,
                           const int32_t* w, int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out, void* stream);
+int bgn_sparse_lincomb_batch_dev(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, size_t nnz, size_t row_max, int level,
+                                 const uint8_t* ct, const uint32_t* row_ptr, const uint32_t* col, const int32_t* w,
+                                 int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out, void* stream);
 int bgn_scan_batch_dev(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
                        size_t r_len, uint8_t* out, void* stream);
 int bgn_mult_batch_dev(bgn_ctx* ctx, size_t count, const uint8_t* a, const uint8_t* b, const uint8_t* r_be,

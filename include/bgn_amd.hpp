@@ -484,6 +484,25 @@ class PublicKey {
           "bgn_lincomb_batch");
     return split(out, level == 2);
   }
+  // Sparse linear map (bgn_sparse_lincomb_batch): a holds nvec vectors of d ciphertexts; (row_ptr, col, w) is a
+  // compressed-row structure of row_ptr.size() - 1 rows shared by the vectors; result v*nrows + i is the sum of
+  // w[e] * a[v*d + col[e]] over the entries of row i.  row_max bounds the rows' lengths; indices outside nnz / d / row_max
+  // contribute nothing.  r: one blinding scalar per result.
+  std::vector<Ciphertext> SparseLinCombBatch(const std::vector<Ciphertext>& a, size_t d, const std::vector<uint32_t>& row_ptr,
+                                             const std::vector<uint32_t>& col, const std::vector<int32_t>& w, size_t row_max,
+                                             int w_bits, const std::vector<Scalar>* r = nullptr) const {
+    if (!d || row_ptr.empty() || col.size() != w.size() || a.size() % d)
+      throw Error(BGN_E_ARG, "row_ptr must hold nrows + 1 entries, col and w one per nonzero, a whole vectors of d ciphertexts");
+    const size_t nrows = row_ptr.size() - 1, nvec = a.size() / d;
+    const int level = a.empty() || !a[0].L2 ? 1 : 2;
+    size_t rl = 0;
+    Bytes A = join(a), rb, out(nvec * nrows * E_);
+    if (r) rb = pack(*r, rl);
+    check(bgn_sparse_lincomb_batch(h_, nvec, nrows, d, col.size(), row_max, level, A.data(), row_ptr.data(), col.data(), w.data(),
+                                   w_bits, r ? rb.data() : nullptr, rl, out.data()),
+          "bgn_sparse_lincomb_batch");
+    return split(out, level == 2);
+  }
   // Prefix sums (bgn_scan_batch): the running sums of every segment of seg_len consecutive elements — the chain of
   // Add (bgn.go:442-497) a running total is computed with; r: one blinding scalar per output.
   std::vector<Ciphertext> ScanBatch(const std::vector<Ciphertext>& a, size_t seg_len, const std::vector<Scalar>* r = nullptr) const {
