@@ -338,6 +338,137 @@ inline LinPlan plan_lincomb(size_t nvec, size_t nrows, size_t d, int w_bits, siz
   return p;
 }
 
+// The bucket method for the same map (bucketops.hpp): no table; per (row, window) the columns are sorted into H buckets
+// by digit, the buckets summed in runs of R by ceil(log_R d) reduce passes, and the bucket sums folded.  Priced in the
+// units of plan_lincomb, step by step as built:
+//   sort     three launches of one thread per (row, column), nwin atomics each: bkt_sort_cost products per window and
+//            round — set from the sort's share of the 1 x 1 x 2^20 rows of profiles/r14_bucket_lincomb_rates.csv;
+//   reduce   pass p launches nvec * nruns[p] lanes (the bound the host knows: nruns[0] = nrows * nwin * (ceil(d/R) + H),
+//            nruns[p] = ceil(nruns[p-1] / R) + nb), a lane costs R additions and its conversion;
+//   fold     stage 1: min(g, H) additions and a conversion, stage 2 (H > g): H/g additions and a conversion, stage 3:
+//            nwin * omega doublings and additions and the final conversion — the dependent depth that is built.
+// Buckets are per row and nothing is shared between rows, so every term grows with nrows: the estimate never falls as
+// nrows grows at fixed d, while the table path's table is paid once.  The window and R are the cheapest admissible
+// pair: the lists' slots must fit 32-bit cursors, the partials 2^28 elements, the workspace `budget_bytes` (at
+// `elem_bytes` per partial).  `table_cost` prices the plan of plan_lincomb the same way, with the fold of its chunks by
+// plan_sum, and the buckets are taken where they are cheaper by kBktMargin — never below kBktMinCols columns: the profile
+// has a gain at 2^20 columns under one row and none at 2^18 under four, 2^14 under 64 or 1024 under 1024, and nothing
+// between was measured — always or never with lin_buckets = 1 / 0.  A forced window is clamped to 1 .. 8, a forced R to 2 .. kBktMaxRun; a forced pair that is not
+// admissible leaves use = false: the caller falls back to the table path.
+constexpr size_t kBktMinCols = (size_t)1 << 20;
+constexpr double kBktMargin = 0.95;        // the estimates are good to about 5 %: a tie stays with the tables
+constexpr int64_t kBktMaxRun = 256;
+constexpr int kBktFoldGroup = 16;
+constexpr int kBktMaxPasses = 28;          // R >= 2, d <= 2^28
+// The sort, per window and round of 65536 (row, column) threads, in products: the milliseconds per window the sort of
+// 2^20 columns of one row measured under every window (profiles/r14_bucket_lincomb_rates.csv, rows "lin_bucket_window
+// 4 .. 8" and the 8-bit rows; 16 rounds; narrower windows, where still more columns meet in one cursor, are priced as 4),
+// over what a product of the table path measures there (11.3 us on level 1, 17 us on level 2).
+inline double bkt_sort_cost(int level, int omega) {
+  static const double ms[kLinPlanMaxWindow + 1] = {0, 2.2, 2.2, 2.2, 2.2, 2.2, 1.25, 1.85, 2.1};
+  return ms[omega] / 16 / (level == 1 ? 0.0113 : 0.017);
+}
+// A lane-round of the reduce passes and the fold against one of the walk, per product counted: every step is one
+// addition of an element that is read once, with no digit plane and no table gather (1 x 1 x 2^20 at 16 bits: 19.8 ms for
+// 2478 products on level 1, 5.6 ms for 462 on level 2, against 11.1 and 18 us per product of the table path).
+constexpr double kBktLaneRate = 0.72;
+
+struct BktPlan {
+  bool use = false;
+  int omega = 0, nwin = 0, npass = 0;
+  uint32_t R = 0;
+  int nc = 0;                              // groups of kBktFoldGroup buckets per window
+  size_t nb = 0;                           // buckets: nrows * nwin * H
+  size_t nruns[kBktMaxPasses] = {};        // runs per vector of pass p (bound)
+  size_t cap[2] = {};                      // elements per vector of the two arrays of partials: passes in turns, then the fold
+  size_t bytes = 0;                        // the path's workspace beyond the decoded vectors and the tail's arrays
+  double cost = 0, table_cost = 0;
+};
+
+inline int bkt_passes(size_t d, size_t R) {
+  int n = 1;
+  for (size_t len = (d + R - 1) / R; len > 1; len = (len + R - 1) / R) ++n;
+  return n;
+}
+
+// The shape of the path at (omega, R); false where the kernels cannot run it.
+inline bool bkt_shape(BktPlan& p, size_t nvec, size_t nrows, size_t d, int w_bits, int omega, size_t R, size_t elem_bytes) {
+  const size_t H = (size_t)1 << (omega - 1);
+  p.omega = omega;
+  p.nwin = lin_plan_windows(w_bits, omega);
+  p.R = (uint32_t)R;
+  p.nc = (int)((H + kBktFoldGroup - 1) / kBktFoldGroup);
+  p.nb = nrows * (size_t)p.nwin * H;
+  p.npass = bkt_passes(d, R);
+  p.nruns[0] = nrows * (size_t)p.nwin * ((d + R - 1) / R + H);
+  for (int k = 1; k < p.npass; ++k) p.nruns[k] = (p.nruns[k - 1] + R - 1) / R + p.nb;
+  if (p.nruns[0] > 0xffffffffu / R || p.nruns[0] > kMaxBatch / nvec) return false;
+  p.cap[0] = p.cap[1] = p.nb;                                                // (a stage of the fold writes at most nb per vector)
+  for (int k = 0; k < p.npass; ++k)
+    if (p.nruns[k] > p.cap[k & 1]) p.cap[k & 1] = p.nruns[k];
+  if (p.cap[0] > kMaxBatch / nvec || p.cap[1] > kMaxBatch / nvec) return false;
+  p.bytes = p.nruns[0] * R * 4 + (2 * (size_t)p.npass + 2) * p.nb * 4 + (nvec * (p.cap[0] + p.cap[1]) + 128) * elem_bytes + 4096;
+  return true;
+}
+
+inline double bkt_cost(const BktPlan& p, size_t nvec, size_t nrows, size_t d, int level, size_t chip_lanes) {
+  const LinCost k = lin_cost(level);
+  const auto rounds = [&](size_t lanes) { return (double)((lanes + chip_lanes - 1) / chip_lanes); };
+  const size_t H = (size_t)1 << (p.omega - 1), nout = nvec * nrows, nq = nout * (size_t)p.nwin * (size_t)p.omega;
+  double c = 0;
+  // (of the nruns[i] lanes launched, at most nruns[i] - nb runs are full; the others end early or exit at once)
+  for (int i = 0; i < p.npass; ++i) c += rounds(nvec * (p.nruns[i] - p.nb)) * (p.R * k.c_add + k.c_fin);
+  c += rounds(nq * (size_t)p.nc) * ((double)(H < (size_t)kBktFoldGroup ? H : (size_t)kBktFoldGroup) * k.c_add + k.c_fin);
+  if (p.nc > 1) c += rounds(nq) * (p.nc * k.c_add + k.c_fin);
+  c += rounds(nout) * ((double)p.nwin * p.omega * (k.c_dbl + k.c_add) + k.c_fin);
+  return c * kBktLaneRate + rounds(nrows * d) * p.nwin * bkt_sort_cost(level, p.omega);
+}
+
+// What plan_lincomb's plan costs, the fold of its chunks included.
+inline double lin_table_cost(const LinPlan& t, size_t nvec, size_t nrows, size_t d, int level, size_t chip_lanes) {
+  const LinCost k = lin_cost(level);
+  const auto rounds = [&](size_t lanes) { return (double)((lanes + chip_lanes - 1) / chip_lanes); };
+  const size_t nout = nvec * nrows;
+  const double H = (double)((size_t)1 << (t.omega - 1)), run = (double)((d + t.nchunk - 1) / t.nchunk);
+  double c = (t.omega > 1 ? rounds(nvec * d) * (H - 1) * k.c_table : 0) +
+             rounds(nout * t.nchunk) * (run * t.nwin * k.c_add + (double)(t.nwin - 1) * t.omega * k.c_dbl + k.c_fin);
+  if (t.nchunk > 1) {
+    const SumPlan f = plan_sum(nout, t.nchunk, level == 1 ? chip_lanes : 2 * chip_lanes, -1, level == 1 ? 4 : 2);
+    size_t len = t.nchunk;
+    for (int i = 0; i < f.passes; ++i) {
+      c += rounds(nout * f.split[i]) * ((double)((len + f.split[i] - 1) / f.split[i]) * k.c_add + k.c_fin);
+      len = f.split[i];
+    }
+  }
+  return c;
+}
+
+inline BktPlan plan_lincomb_buckets(size_t nvec, size_t nrows, size_t d, int w_bits, size_t budget_bytes, size_t entry_bytes,
+                                    size_t elem_bytes, int level, size_t chip_lanes, int64_t forced_window, int64_t forced_split,
+                                    int64_t buckets, int64_t bucket_window, int64_t bucket_run) {
+  BktPlan best;
+  if (!nvec || !nrows || !d || w_bits < 1 || w_bits > 31) return best;
+  if (!chip_lanes) chip_lanes = 1;
+  const LinPlan t = plan_lincomb(nvec, nrows, d, w_bits, budget_bytes, entry_bytes, level, chip_lanes, forced_window, forced_split);
+  const double table_cost = lin_table_cost(t, nvec, nrows, d, level, chip_lanes);
+  const int w0 = bucket_window >= 1 ? (int)(bucket_window > kLinPlanMaxWindow ? kLinPlanMaxWindow : bucket_window) : 1;
+  const int w1 = bucket_window >= 1 ? w0 : kLinPlanMaxWindow;
+  const size_t r0 = bucket_run >= 1 ? (size_t)(bucket_run < 2 ? 2 : bucket_run > kBktMaxRun ? kBktMaxRun : bucket_run) : 2;
+  const size_t r1 = bucket_run >= 1 ? r0 : 64;
+  bool found = false;
+  for (int omega = w0; omega <= w1; ++omega)
+    for (size_t R = r0; R <= r1; R *= 2) {
+      BktPlan p;
+      if (!bkt_shape(p, nvec, nrows, d, w_bits, omega, R, elem_bytes) || p.bytes > budget_bytes) continue;
+      p.cost = bkt_cost(p, nvec, nrows, d, level, chip_lanes);
+      if (!found || p.cost < best.cost) best = p;
+      found = true;
+    }
+  best.table_cost = table_cost;
+  best.use = found && buckets != 0 && (buckets > 0 || (d >= kBktMinCols && best.cost < kBktMargin * table_cost));
+  return best;
+}
+
 // Sparse linear maps (sparseops.hpp): out[v][r] = sum_{e in row r} w[e] * ct[v][col[e]], nnz entries in rows of at most
 // row_max.  The planner counts nonzeros, not nrows * d, and never sees the index arrays: a lane's run is taken at its
 // bound rm = min(row_max, nnz) (a wave costs its longest row anyway).  The constants are those of plan_lincomb.

@@ -1784,6 +1784,94 @@ int lincomb_check(const bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int lev
     return fail(BGN_E_ARG, "batch too large (max 2^28 ciphertexts, weights and results per call)");
   return BGN_OK;
 }
+
+// The path without tables (bucketops.hpp), planned by dispatch.hpp plan_lincomb_buckets: the vectors are decoded once,
+// the columns sorted by the digits of their weights (count, offsets, scatter: nothing is read back), the buckets summed
+// by the reduce passes and folded; the tail — encode, blinding — is that of the table path.  Called with the context
+// locked and the stream ordered.
+int lincomb_buckets_dev(bgn_ctx* c, const BktPlan& bp, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct,
+                        const int32_t* w, int w_bits, const uint8_t* r_be, size_t r_len, uint8_t* out, hipStream_t s) {
+  const KernelTable* kt = c->kt;
+  const size_t ncols = nvec * d, nout = nvec * nrows, E = 2 * (size_t)c->L, nb = bp.nb, R = bp.R;
+  const size_t sc = round_up(ncols, 64), so = round_up(nout, 64);
+  SoA2 A, Pt[2], W, O, T1, T2;
+  uint32_t *ent = nullptr, *cnt = nullptr, *rs = nullptr, *cur = nullptr, *prefix = nullptr;
+  uint8_t* res = nullptr;
+  if (int rc = carve(c, [&](Ws& ws) {
+    A = level == 1 ? ws.g1(sc) : ws.gt(sc);
+    ent = (uint32_t*)ws.cv.take(bp.nruns[0] * R * 4);
+    cnt = (uint32_t*)ws.cv.take((size_t)(bp.npass + 1) * nb * 4);
+    rs = (uint32_t*)ws.cv.take((size_t)bp.npass * nb * 4);
+    cur = (uint32_t*)ws.cv.take(nb * 4);
+    for (int i = 0; i < 2; ++i)
+      Pt[i] = level == 1 ? ws.g1(round_up(nvec * bp.cap[i], 64)) : ws.gt(round_up(nvec * bp.cap[i], 64));
+    W = level == 1 ? ws.g1(so) : ws.gt(so);
+    if (r_be) {
+      res = (uint8_t*)ws.cv.take(nout * E + 16);
+      if (level == 1) { O = ws.g1(so); T1 = ws.g1(so); T2 = ws.g1(so); prefix = ws.fp(so); }
+      else { O = ws.gt(so); T1 = ws.gt(so); T2 = ws.gt(so); }
+    }
+  })) return rc;
+  kt->decode(s, c->d_params, ct, c->L, ncols, A, nullptr, nullptr);
+  HIP_TRY(hipEventRecord(c->ev2, s));
+  BktSortArgs sa;
+  sa.w = w; sa.nrows = nrows; sa.d = d; sa.w_bits = w_bits; sa.omega = bp.omega; sa.nwin = bp.nwin;
+  sa.cnt = cnt; sa.ent = nullptr;
+  kt->bkt_zero(s, cnt, nb);
+  kt->bkt_count(s, sa);
+  BktOffsetsArgs oa;
+  oa.cnt = cnt; oa.rs = rs; oa.cur = cur; oa.nb = nb; oa.R = bp.R; oa.npass = bp.npass;
+  kt->bkt_offsets(s, oa);
+  sa.cnt = cur; sa.ent = ent;
+  kt->bkt_scatter(s, sa);
+  HIP_TRY(hipEventRecord(c->ev3, s));
+  c->ev2_valid = true;
+  c->aux_kernel = "k_bkt_scatter";
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  const auto io = [](const SoA2& src, const SoA2& dst) {
+    BktIo i;
+    i.sx = src.c0; i.sy = src.c1; i.sinf = src.inf; i.ss = src.stride;
+    i.ox = dst.c0; i.oy = dst.c1; i.oinf = dst.inf; i.so = dst.stride;
+    return i;
+  };
+  for (int p = 0; p < bp.npass; ++p) {
+    BktReduceArgs ra;
+    ra.io = io(p ? Pt[(p - 1) & 1] : A, Pt[p & 1]);
+    ra.ent = p ? nullptr : ent;
+    ra.cnt = cnt + (size_t)p * nb; ra.rs = rs + (size_t)p * nb; ra.prs = p ? rs + (size_t)(p - 1) * nb : nullptr;
+    ra.nvec = nvec; ra.nb = nb; ra.nruns = bp.nruns[p]; ra.sper = p ? bp.nruns[p - 1] : d;
+    ra.R = bp.R;
+    kt->bkt_reduce(s, c->d_params, c->d_consts, level, ra);
+  }
+  int at = (bp.npass - 1) & 1;         // the array that holds the bucket sums, then each stage's result
+  BktFoldArgs fa;
+  fa.cnt = cnt + (size_t)bp.npass * nb; fa.rs = rs + (size_t)(bp.npass - 1) * nb;
+  fa.nvec = nvec; fa.nrows = nrows; fa.sper = bp.nruns[bp.npass - 1];
+  fa.nwin = bp.nwin; fa.omega = bp.omega; fa.g = kBktFoldGroup; fa.nc = bp.nc;
+  for (int stage = 1; stage <= 3; ++stage) {
+    if (stage == 2 && bp.nc == 1) continue;
+    fa.stage = stage;
+    fa.io = io(Pt[at], stage == 3 ? W : Pt[at ^ 1]);
+    kt->bkt_fold(s, c->d_params, c->d_consts, level, fa);
+    at ^= 1;
+  }
+  kt->encode(s, level == 1 ? W.inf : nullptr, W.c0, W.c1, W.stride, c->L, nout, r_be ? res : out);
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->last_kernel = level == 1 ? "k_bkt_reduce_g1" : "k_bkt_reduce_gt";
+  c->ev_valid = true;
+  if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
+    kt->decode_plain(s, c->d_params, res, c->L, nout, O);
+    if (level == 1) {
+      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, nout);
+      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, nout, out);
+    } else {
+      blind_l2(c, s, O, r_be, r_len, T1, T2, nout);
+      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, nout, out);
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
 }  // namespace
 
 int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
@@ -1808,6 +1896,13 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
   const size_t entry_bytes = level == 1 ? 4 * (size_t)c->nl * 4 + 1 : 2 * (size_t)c->nl * 4;
   size_t avail = 0;
   if (!ctx_free_memory(c, &avail, c->arena_bytes)) avail = 0;
+  if (kt->bkt_reduce) {                // the path without tables, where it is planned or forced and its workspace fits
+    const BktPlan bp = plan_lincomb_buckets(nvec, nrows, d, w_bits, avail / 2, entry_bytes, 2 * (size_t)c->nl * 4 + 1, level,
+                                            kSumChipLanes, opt(c, &Options::lin_window), opt(c, &Options::lin_split),
+                                            opt(c, &Options::lin_buckets), opt(c, &Options::lin_bucket_window),
+                                            opt(c, &Options::lin_bucket_run));
+    if (bp.use) return lincomb_buckets_dev(c, bp, nvec, nrows, d, level, ct, w, w_bits, r_be, r_len, out, s);
+  }
   const LinPlan plan = plan_lincomb(nvec, nrows, d, w_bits, avail / 2, entry_bytes, level, kSumChipLanes,
                                     opt(c, &Options::lin_window), opt(c, &Options::lin_split));
   const size_t nchunk = plan.nchunk, npart = nout * nchunk;

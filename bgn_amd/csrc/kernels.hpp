@@ -268,6 +268,48 @@ struct SpWalkArgs {
   uint32_t row_max;
 };
 
+// The bucket method of the dense linear map (bucketops.hpp): no tables; the columns of a row are sorted by the digit of
+// each window into nb = nrows * nwin * H buckets (bucket (r*nwin + t)*H + |digit| - 1), summed per bucket in runs of R,
+// and the bucket sums folded.
+struct BktSortArgs {
+  const int32_t* w; size_t nrows, d;
+  int w_bits, omega, nwin;
+  uint32_t* cnt;                                                            // k_bkt_count: the histogram, nb words, zero before
+                                                                            // k_bkt_scatter: the cursors (first free slot per bucket)
+  uint32_t* ent;                                                            // k_bkt_scatter: the lists, column | sign << 31
+};
+// cnt row 0 is the histogram; row p + 1 is written: the runs of pass p per bucket = the elements of pass p + 1.
+// rs row p is written: the first run of every bucket in pass p.  cur[b] = rs[0][b] * R, the start of bucket b's list.
+struct BktOffsetsArgs {
+  uint32_t* cnt; uint32_t* rs; uint32_t* cur;
+  size_t nb; uint32_t R; int npass;
+};
+// Elements read and partials written by the reduce passes and the fold: limb-major SoA, canonical Montgomery (the last
+// step of the fold writes plain canonical); the flags are null on level 2.
+struct BktIo {
+  const uint32_t* sx; const uint32_t* sy; const uint8_t* sinf; size_t ss;
+  uint32_t* ox; uint32_t* oy; uint8_t* oinf; size_t so;
+};
+// One reduce pass: lane v*nruns + run sums the (at most R) elements of its run into partial v*nruns + run.  Pass 0
+// (ent != null) gathers columns of the decoded vectors (sper = d) by the lists; a later pass reads the partials of the
+// pass before (sper = its nruns), those of bucket b from prs[b] on.
+struct BktReduceArgs {
+  BktIo io;
+  const uint32_t* ent; const uint32_t* cnt; const uint32_t* rs; const uint32_t* prs;
+  size_t nvec, nb, nruns, sper;
+  uint32_t R;
+};
+// The fold, sum_b b * B_b over the bits of b.  Stage 1: lane (((v*nrows + r)*nwin + t)*omega + k)*nc + c sums the
+// buckets b of group c (g buckets) with bit k of b set, found through the last pass's cnt (0 or 1) and rs.  Stage 2
+// (nc > 1): lane q sums the partials q*nc .. q*nc + nc - 1.  Stage 3: lane o = v*nrows + r walks the nbits = nwin * omega
+// sums o*nbits + s from the top: a doubling, an addition; plain canonical out.
+struct BktFoldArgs {
+  BktIo io;
+  const uint32_t* cnt; const uint32_t* rs;
+  size_t nvec, nrows, sper;
+  int nwin, omega, g, nc, stage;
+};
+
 // Prefix sums (scanops.hpp).  One launch: lanes [q0, q1) of the nseg * nch chunk lanes.  totals != 0: write chunk q's
 // total to out[q] and nothing else (off unused); otherwise write every prefix to its element's place in `out`, starting from off[q - 1] (the
 // inclusive scan of the totals, nseg x nch) when `off` is given and the chunk is not its segment's first.
@@ -410,9 +452,17 @@ struct KernelTable {
   // sparse linear maps (sparseops.hpp): the digit planes of the entries' weights and the walk over the rows' entries
   void (*sp_digits)(hipStream_t s, SpDigitsArgs a);
   void (*sp_walk)(hipStream_t s, const void* params, const PairingConsts* consts, int level, SpWalkArgs a);
+  // the bucket method of the dense linear map (bucketops.hpp): the sort (zero, count, offsets, scatter), one reduce pass,
+  // one stage of the fold
+  void (*bkt_zero)(hipStream_t s, uint32_t* p, size_t n);
+  void (*bkt_count)(hipStream_t s, BktSortArgs a);
+  void (*bkt_offsets)(hipStream_t s, BktOffsetsArgs a);
+  void (*bkt_scatter)(hipStream_t s, BktSortArgs a);
+  void (*bkt_reduce)(hipStream_t s, const void* params, const PairingConsts* consts, int level, BktReduceArgs a);
+  void (*bkt_fold)(hipStream_t s, const void* params, const PairingConsts* consts, int level, BktFoldArgs a);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
-  Entry entries[28];
+  Entry entries[32];
 };
 
 const KernelTable* kernel_table_nl3();

@@ -15,6 +15,7 @@
 #include "scanops.hpp"
 #include "linops.hpp"
 #include "sparseops.hpp"
+#include "bucketops.hpp"
 
 namespace bgn {
 
@@ -1432,6 +1433,119 @@ static void launch_sp_walk(hipStream_t s, const void* params, const PairingConst
                        consts, a);
 }
 
+// ---- the bucket method of the dense linear map (bucketops.hpp) ---------------------------------------------------
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_bkt_zero(u32* p, size_t n) {
+  const size_t i = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  if (i < n) p[i] = 0;
+}
+
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_bkt_count(BktSortArgs A) {
+  __shared__ u32 h[kBktMaxBins];
+  bkt_count_block(A, h);
+}
+
+template <int NL>
+__global__ void __launch_bounds__(kBktScanBlock)
+k_bkt_offsets(BktOffsetsArgs A) {
+  __shared__ u32 part[kBktScanBlock];
+  bkt_offsets_block(A, part);
+}
+
+template <int NL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_bkt_scatter(BktSortArgs A) {
+  bkt_scatter_lane(A);
+}
+
+template <int NL, int LEVEL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_bkt_reduce(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, BktReduceArgs A) {
+  __shared__ LFp<NL> L[4];
+  const size_t total = A.nvec * A.nruns;
+  size_t lane = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  const bool live = lane < total;
+  if (!__ballot(live)) return;
+  if (!live) lane = total - 1;               // keep every index in range; nothing is taken or stored
+  const BktRunSrc src = bkt_run(A, lane, live);
+  if (!__ballot(src.n != 0)) return;         // a wave of runs past the live ones: before any load of an element
+  if (LEVEL == 1)
+    bkt_sum_g1<NL>(src, A.R, A.io, lane, src.n != 0, L, C, P);
+  else
+    bkt_sum_gt<NL>(src, A.R, A.io, lane, src.n != 0, L, P);
+}
+
+template <int NL, int LEVEL>
+__global__ void __launch_bounds__(FP_BLOCK)
+k_bkt_fold(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, BktFoldArgs A) {
+  __shared__ LFp<NL> L[4];
+  const size_t nout = A.nvec * A.nrows, nq = nout * (size_t)A.nwin * (size_t)A.omega;
+  const size_t total = A.stage == 1 ? nq * (size_t)A.nc : A.stage == 2 ? nq : nout;
+  size_t lane = (size_t)blockIdx.x * FP_BLOCK + threadIdx.x;
+  const bool live = lane < total;
+  if (!__ballot(live)) return;
+  if (!live) lane = total - 1;
+  if (A.stage == 3) {                        // (uniform)
+    if (LEVEL == 1)
+      bkt_horner_g1<NL>(A, lane, live, L, C, P);
+    else
+      bkt_horner_gt<NL>(A, lane, live, L, P);
+    return;
+  }
+  const BktFoldSrc src = bkt_fold_src(A, lane, live);
+  const u32 steps = (u32)(A.stage == 1 ? A.g : A.nc);
+  if (LEVEL == 1)
+    bkt_sum_g1<NL>(src, steps, A.io, lane, live, L, C, P);
+  else
+    bkt_sum_gt<NL>(src, steps, A.io, lane, live, L, P);
+}
+
+static void launch_bkt_zero(hipStream_t s, uint32_t* p, size_t n) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_bkt_zero<NL_>, dim3(grid_for(n)), dim3(FP_BLOCK), 0, s, p, n);
+}
+
+static void launch_bkt_count(hipStream_t s, BktSortArgs a) {
+  if (!a.nrows || !a.d) return;
+  hipLaunchKernelGGL(k_bkt_count<NL_>, dim3((unsigned)(a.nrows * grid_for(a.d))), dim3(FP_BLOCK), 0, s, a);
+}
+
+static void launch_bkt_offsets(hipStream_t s, BktOffsetsArgs a) {
+  if (!a.nb) return;
+  hipLaunchKernelGGL(k_bkt_offsets<NL_>, dim3(1), dim3(kBktScanBlock), 0, s, a);
+}
+
+static void launch_bkt_scatter(hipStream_t s, BktSortArgs a) {
+  if (!a.nrows || !a.d) return;
+  hipLaunchKernelGGL(k_bkt_scatter<NL_>, dim3((unsigned)(a.nrows * grid_for(a.d))), dim3(FP_BLOCK), 0, s, a);
+}
+
+static void launch_bkt_reduce(hipStream_t s, const void* params, const PairingConsts* consts, int level, BktReduceArgs a) {
+  const size_t total = a.nvec * a.nruns;
+  if (!total) return;
+  if (level == 1)
+    hipLaunchKernelGGL((k_bkt_reduce<NL_, 1>), dim3(grid_for(total)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+  else
+    hipLaunchKernelGGL((k_bkt_reduce<NL_, 2>), dim3(grid_for(total)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+}
+
+static void launch_bkt_fold(hipStream_t s, const void* params, const PairingConsts* consts, int level, BktFoldArgs a) {
+  const size_t nout = a.nvec * a.nrows, nq = nout * (size_t)a.nwin * (size_t)a.omega;
+  const size_t total = a.stage == 1 ? nq * (size_t)a.nc : a.stage == 2 ? nq : nout;
+  if (!total) return;
+  if (level == 1)
+    hipLaunchKernelGGL((k_bkt_fold<NL_, 1>), dim3(grid_for(total)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+  else
+    hipLaunchKernelGGL((k_bkt_fold<NL_, 2>), dim3(grid_for(total)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params,
+                       consts, a);
+}
+
 template <int NL>
 __global__ void __launch_bounds__(FP_BLOCK)
 k_poly_split(const FpParams<NL>* __restrict__ P, const PairingConsts* __restrict__ C, PolySplitArgs A) {
@@ -1726,6 +1840,12 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
       launch_scan_wire,
       launch_sp_digits,
       launch_sp_walk,
+      launch_bkt_zero,
+      launch_bkt_count,
+      launch_bkt_offsets,
+      launch_bkt_scatter,
+      launch_bkt_reduce,
+      launch_bkt_fold,
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1759,6 +1879,10 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
 #endif
        {"k_sp_walk_g1", (const void*)k_sp_walk<NL_, 1>},
        {"k_sp_walk_gt", (const void*)k_sp_walk<NL_, 2>},
+       {"k_bkt_reduce_g1", (const void*)k_bkt_reduce<NL_, 1>},
+       {"k_bkt_reduce_gt", (const void*)k_bkt_reduce<NL_, 2>},
+       {"k_bkt_fold_g1", (const void*)k_bkt_fold<NL_, 1>},
+       {"k_bkt_fold_gt", (const void*)k_bkt_fold<NL_, 2>},
        {nullptr, nullptr}},
   };
   return &t;

@@ -67,7 +67,11 @@ struct Options {
                            // dispatch.hpp plan_lincomb; narrowed until the tables fit the memory budget — same bytes)
   V lin_split{-1};         // ... and the chunks the columns of one output are cut into (-1: planned; k >= 1: forced, clamped
                            // to the number of columns — same bytes)
-  V poly_karatsuba{1};     // Karatsuba levels on square MultPoly products
+  V lin_buckets{-1};       // linear maps by the bucket method, without tables (bucketops.hpp): -1 planned (dispatch.hpp
+                           // plan_lincomb_buckets: long vectors under few rows), 0 never, 1 always — same bytes
+  V lin_bucket_window{-1}; // ... its window width, 1 .. 8 (-1: planned)
+  V lin_bucket_run{-1};    // ... and the entries of a bucket one lane of a reduce pass sums, 2 .. 256 (-1: planned)
+  V poly_karatsuba{1};    // Karatsuba levels on square MultPoly products
   V poly_levels{-1};       // forced number of levels (-1: planned)
   V poly_tables{-1};       // per-coefficient line tables: 0 never, 1 always, -1 by size
   V poly_table_max_mb{0};  // cap of those tables (0: default)
@@ -142,6 +146,9 @@ inline const OptionDesc* option_table(size_t* n) {
       {"scan_range", &Options::scan_range, true, nullptr},
       {"lin_window", &Options::lin_window, true, nullptr},
       {"lin_split", &Options::lin_split, true, nullptr},
+      {"lin_buckets", &Options::lin_buckets, true, nullptr},
+      {"lin_bucket_window", &Options::lin_bucket_window, true, nullptr},
+      {"lin_bucket_run", &Options::lin_bucket_run, true, nullptr},
       {"poly_karatsuba", &Options::poly_karatsuba, true, nullptr},
       {"poly_levels", &Options::poly_levels, true, nullptr},
       {"poly_tables", &Options::poly_tables, true, nullptr},

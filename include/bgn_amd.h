@@ -268,6 +268,11 @@ int bgn_sum_batch(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const ui
  * chip, the chunks folded by the passes of bgn_sum_batch — walks the windows from the top with ONE table addition per
  * (row, column, window) (csrc/linops.hpp; omega and the chunks planned by dispatch.hpp plan_lincomb inside the context's
  * memory budget; options lin_window, lin_split — same bytes under every setting).
+ * Two execution paths, identical bytes: one or a few rows over a very long vector share no table, and are served by the
+ * bucket method instead (csrc/bucketops.hpp) — the columns sorted on the device by the digits of their weights, the
+ * buckets summed in runs and folded, no table built; planned by dispatch.hpp plan_lincomb_buckets, never below 1024
+ * columns; options lin_buckets (-1 planned, 0 never, 1 always), lin_bucket_window (1 .. 8), lin_bucket_run (2 .. 256).
+ * Where its workspace does not fit the context's memory budget the table path serves.
  * Replaces the loops of MultConst (bgn.go:253-291) and Add (bgn.go:442-497) a weighted sum, a linear layer, EvalPoly or
  * MultConstPoly is computed with. */
 int bgn_lincomb_batch(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
