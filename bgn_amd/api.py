@@ -148,7 +148,9 @@ class Engine:
         """Linear map (bgn_lincomb_batch): `ct` holds nvec vectors of d elements, `W` is an integer nrows x d array of
         plaintext weights; row v*nrows + i of the result is sum_j W[i][j] * ct[v][j] (level 1: G1, level 2: powers and
         products in GT), blinded with one r per result if given.  w_bits: the bound on |W| in bits (default: the bit
-        length of the largest |W|); a weight counts as sign(w) * (|w| mod 2^w_bits)."""
+        length of the largest |W|); a weight counts as sign(w) * (|w| mod 2^w_bits).  The bytes do not depend on the path
+        the engine plans: window tables per ciphertext, buckets for one long row, or — many rows at w_bits <= 4 —
+        tables per group of columns (option lin_groups)."""
         A = _as_u8(ct, self.elem_bytes)
         Wa = np.asarray(W)
         if Wa.ndim != 2 or Wa.dtype.kind not in "iu":

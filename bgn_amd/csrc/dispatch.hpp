@@ -469,6 +469,123 @@ inline BktPlan plan_lincomb_buckets(size_t nvec, size_t nrows, size_t d, int w_b
   return best;
 }
 
+// Column groups for the same map under narrow weights (groupops.hpp): g consecutive ciphertexts share a table of their
+// M = (3^g - 1) / 2 signed combinations, and an output costs one addition per group and bit plane.  Priced in the units of
+// plan_lincomb:
+//   table    one lane per group (ngr = nvec * ceil(d / g) lanes), M entries each: on level 1 an affine addition of a
+//            shared-inversion run (grp_step: 7 products) and g inversions of c_fin; on level 2 one product in F_p^2;
+//   walk     nout * nchunk lanes; a lane adds ceil(ngroups / nchunk) * w_bits entries, doubles w_bits - 1 times, converts;
+//   fold     of the chunks by plan_sum, as lin_table_cost prices it.
+// The table is a dependent chain of M steps on few lanes, so the path pays only where the walk it shortens is longer
+// than that chain: many rows under a long vector.  `groups`: 0 never; 2 .. 6 that group size (other positive values
+// clamped), always; -1 the cheapest size, taken where nrows >= kGrpMinRows, d >= kGrpMinCols and the estimate is below
+// kGrpMargin of lin_table_cost.  Either way g is narrowed until nvec * ngroups * M entries fit `budget_bytes` at `entry_bytes` each
+// and 2^28 elements; if g = 2 does not fit, or w_bits > kGrpPlanMaxBits, use = false: the table path.  `table` is
+// plan_lincomb's plan under the same arguments, whatever is decided.
+// forced_split >= 1: the chunk count, clamped to the number of groups (chunks are whole groups).
+constexpr int kGrpPlanMaxBits = 4;         // (restated from grprecode.hpp, as the window constants above)
+constexpr int kGrpPlanMinGroup = 2, kGrpPlanMaxGroup = 6;
+// profiles/r15_group_lincomb_rates.csv (MI355X, 1024-bit key): 1 x 4096 x 4096 and 1 x 16384 x 1024 gain at one and two
+// bits on both levels (level 1, one bit: 12.6 against 27.5 ms and 11.6 against 26.2 ms, at the planned g = 4);
+// 1 x 1024 x 1024, 64 x 16 x 256 and 1 x 16 x 1024 lose at every group size tried (the table's chain alone is 3.4 ms at
+// g = 4 and 9 ms at g = 5 on level 1, where the whole table path takes 5 ms), and nothing between was measured: the floors
+// are the smallest row and column counts with a measured gain.  The estimates at the gaining shapes are 0.4 .. 0.7 of
+// the tables', at the losing ones 0.85 and more.
+constexpr size_t kGrpMinRows = 4096, kGrpMinCols = 1024;
+constexpr double kGrpMargin = 0.8;
+inline size_t grp_plan_entries(int g) {
+  size_t p = 1;
+  for (int i = 0; i < g; ++i) p *= 3;
+  return (p - 1) / 2;
+}
+
+struct GrpPlan {
+  bool use = false;
+  int g = 0;
+  size_t M = 0, ngroups = 0, nchunk = 0;
+  size_t entries = 0;                      // nvec * ngroups * M
+  double cost = 0, table_cost = 0;
+  LinPlan table;
+};
+
+inline bool grp_shape(GrpPlan& p, size_t nvec, size_t nrows, size_t d, int w_bits, int g, size_t budget_bytes, size_t entry_bytes,
+                      size_t chip_lanes, int64_t forced_split) {
+  p.g = g;
+  p.M = grp_plan_entries(g);
+  p.ngroups = (d + (size_t)g - 1) / (size_t)g;
+  const size_t ngr = nvec * p.ngroups, nout = nvec * nrows;
+  if (ngr > kMaxBatch / p.M || entry_bytes > budget_bytes || ngr * p.M > budget_bytes / entry_bytes) return false;
+  p.entries = ngr * p.M;
+  size_t nchunk = 1;
+  if (forced_split >= 1) {
+    nchunk = (size_t)forced_split;
+  } else if (nout < chip_lanes) {
+    const size_t by_chip = (chip_lanes + nout - 1) / nout, by_run = p.ngroups * (size_t)w_bits / kLinMinRun;
+    nchunk = by_run < by_chip ? by_run : by_chip;
+  }
+  if (nchunk > p.ngroups) nchunk = p.ngroups;
+  if (nchunk > kMaxBatch / nout) nchunk = kMaxBatch / nout;
+  if (nchunk < 1) nchunk = 1;
+  p.nchunk = nchunk;
+  return true;
+}
+
+inline double grp_cost(const GrpPlan& p, size_t nvec, size_t nrows, int w_bits, int level, size_t chip_lanes) {
+  const LinCost k = lin_cost(level);
+  const auto rounds = [&](size_t lanes) { return (double)((lanes + chip_lanes - 1) / chip_lanes); };
+  const size_t nout = nvec * nrows;
+  const double grp_step = level == 1 ? 7 : 3, run = (double)((p.ngroups + p.nchunk - 1) / p.nchunk);
+  double c = rounds(nvec * p.ngroups) * ((double)p.M * grp_step + (level == 1 ? p.g * k.c_fin : 0)) +
+             rounds(nout * p.nchunk) * (run * w_bits * k.c_add + (double)(w_bits - 1) * k.c_dbl + k.c_fin);
+  if (p.nchunk > 1) {
+    const SumPlan f = plan_sum(nout, p.nchunk, level == 1 ? chip_lanes : 2 * chip_lanes, -1, level == 1 ? 4 : 2);
+    size_t len = p.nchunk;
+    for (int i = 0; i < f.passes; ++i) {
+      c += rounds(nout * f.split[i]) * ((double)((len + f.split[i] - 1) / f.split[i]) * k.c_add + k.c_fin);
+      len = f.split[i];
+    }
+  }
+  return c;
+}
+
+inline GrpPlan plan_lincomb_groups(size_t nvec, size_t nrows, size_t d, int w_bits, size_t budget_bytes, size_t entry_bytes,
+                                   int level, size_t chip_lanes, int64_t forced_window, int64_t forced_split, int64_t groups) {
+  GrpPlan best;
+  if (!nvec || !nrows || !d || w_bits < 1 || w_bits > 31) return best;
+  if (!chip_lanes) chip_lanes = 1;
+  best.table = plan_lincomb(nvec, nrows, d, w_bits, budget_bytes, entry_bytes, level, chip_lanes, forced_window, forced_split);
+  best.table_cost = lin_table_cost(best.table, nvec, nrows, d, level, chip_lanes);
+  if (groups == 0 || w_bits > kGrpPlanMaxBits) return best;
+  const bool forced = groups > 0;
+  const int g1 = !forced ? kGrpPlanMaxGroup
+                         : (int)(groups < kGrpPlanMinGroup ? kGrpPlanMinGroup : groups > kGrpPlanMaxGroup ? kGrpPlanMaxGroup : groups);
+  bool found = false;
+  for (int g = g1; g >= kGrpPlanMinGroup; --g) {
+    GrpPlan p;
+    if (!grp_shape(p, nvec, nrows, d, w_bits, g, budget_bytes, entry_bytes, chip_lanes, forced_split)) continue;
+    p.cost = grp_cost(p, nvec, nrows, w_bits, level, chip_lanes);
+    if (!found || p.cost < best.cost) {
+      p.table = best.table;
+      p.table_cost = best.table_cost;
+      best = p;
+    }
+    found = true;
+    if (forced) break;                     // the widest size that fits, at most the one asked for
+  }
+  best.use = found && (forced || (nrows >= kGrpMinRows && d >= kGrpMinCols && best.cost < kGrpMargin * best.table_cost));
+  return best;
+}
+
+// Which of the three paths of bgn_lincomb_batch runs: a forced bucket path wins over everything, a forced group size
+// over planned buckets, planned buckets (long vectors under few rows) over planned groups (many rows).
+enum class LinPath { Tables, Buckets, Groups };
+inline LinPath lin_path(const BktPlan& b, const GrpPlan& g, int64_t buckets, int64_t groups) {
+  if (buckets > 0 && b.use) return LinPath::Buckets;
+  if (groups > 0 && g.use) return LinPath::Groups;
+  if (b.use) return LinPath::Buckets;
+  return g.use ? LinPath::Groups : LinPath::Tables;
+}
+
 // Sparse linear maps (sparseops.hpp): out[v][r] = sum_{e in row r} w[e] * ct[v][col[e]], nnz entries in rows of at most
 // row_max.  The planner counts nonzeros, not nrows * d, and never sees the index arrays: a lane's run is taken at its
 // bound rm = min(row_max, nnz) (a wave costs its longest row anyway).  The constants are those of plan_lincomb.

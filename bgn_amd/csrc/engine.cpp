@@ -1896,17 +1896,28 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
   const size_t entry_bytes = level == 1 ? 4 * (size_t)c->nl * 4 + 1 : 2 * (size_t)c->nl * 4;
   size_t avail = 0;
   if (!ctx_free_memory(c, &avail, c->arena_bytes)) avail = 0;
-  if (kt->bkt_reduce) {                // the path without tables, where it is planned or forced and its workspace fits
-    const BktPlan bp = plan_lincomb_buckets(nvec, nrows, d, w_bits, avail / 2, entry_bytes, 2 * (size_t)c->nl * 4 + 1, level,
-                                            kSumChipLanes, opt(c, &Options::lin_window), opt(c, &Options::lin_split),
-                                            opt(c, &Options::lin_buckets), opt(c, &Options::lin_bucket_window),
-                                            opt(c, &Options::lin_bucket_run));
-    if (bp.use) return lincomb_buckets_dev(c, bp, nvec, nrows, d, level, ct, w, w_bits, r_be, r_len, out, s);
-  }
-  const LinPlan plan = plan_lincomb(nvec, nrows, d, w_bits, avail / 2, entry_bytes, level, kSumChipLanes,
-                                    opt(c, &Options::lin_window), opt(c, &Options::lin_split));
+  BktPlan bp;                          // the path without tables, where it is planned or forced and its workspace fits
+  if (kt->bkt_reduce)
+    bp = plan_lincomb_buckets(nvec, nrows, d, w_bits, avail / 2, entry_bytes, 2 * (size_t)c->nl * 4 + 1, level,
+                              kSumChipLanes, opt(c, &Options::lin_window), opt(c, &Options::lin_split),
+                              opt(c, &Options::lin_buckets), opt(c, &Options::lin_bucket_window),
+                              opt(c, &Options::lin_bucket_run));
+  // the column groups of narrow weights (groupops.hpp): `plan` becomes their shape — one "column" per group, one
+  // "window" per bit plane, M entries per group — and the decode, the fold of the chunks and the tail are shared
+  GrpPlan gp;
+  if (kt->grp_walk)
+    gp = plan_lincomb_groups(nvec, nrows, d, w_bits, avail / 2, entry_bytes, level, kSumChipLanes,
+                             opt(c, &Options::lin_window), opt(c, &Options::lin_split), opt(c, &Options::lin_groups));
+  const LinPath path = lin_path(bp, gp, opt(c, &Options::lin_buckets), opt(c, &Options::lin_groups));
+  if (path == LinPath::Buckets) return lincomb_buckets_dev(c, bp, nvec, nrows, d, level, ct, w, w_bits, r_be, r_len, out, s);
+  const bool grp = path == LinPath::Groups;
+  LinPlan plan = plan_lincomb(nvec, nrows, d, w_bits, avail / 2, entry_bytes, level, kSumChipLanes,
+                              opt(c, &Options::lin_window), opt(c, &Options::lin_split));
+  if (grp) { plan.nchunk = gp.nchunk; plan.entries = gp.entries; plan.nwin = w_bits; }
   const size_t nchunk = plan.nchunk, npart = nout * nchunk;
   const int H = 1 << (plan.omega - 1);
+  // level 1 of the groups: the prefix products of one level's additions, 3^(g-1) per lane of the table kernel's launch
+  const size_t grp_sp = grp && level == 1 ? round_up(nvec * gp.ngroups, 256) * ((2 * gp.M + 1) / 3) : 0;
   SumPlan fold;
   if (nchunk > 1) fold = plan_sum(nout, nchunk, level == 1 ? kSumChipLanes : 2 * kSumChipLanes, -1, level == 1 ? 4 : 2);
   size_t cap[2] = {0, 0};              // elements of the two arrays of the fold's partials
@@ -1919,10 +1930,12 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
   uint8_t *planes = nullptr, *pw = nullptr, *res = nullptr, *part[2] = {nullptr, nullptr};
   if (int rc = carve(c, [&](Ws& ws) {
     A = level == 1 ? ws.g1(sc) : ws.gt(sc);
-    planes = (uint8_t*)ws.cv.take((size_t)plan.nwin * d * nrows * (size_t)lin_digit_bytes(plan.omega));
+    planes = (uint8_t*)ws.cv.take(grp ? (size_t)w_bits * gp.ngroups * nrows * 2
+                                      : (size_t)plan.nwin * d * nrows * (size_t)lin_digit_bytes(plan.omega));
     if (plan.entries) {
       T = level == 1 ? ws.g1(st) : ws.gt(st);
-      if (level == 1) { tz = ws.fp(st); tp = ws.fp(st); }
+      if (grp_sp) tp = ws.fp(grp_sp);
+      else if (level == 1) { tz = ws.fp(st); tp = ws.fp(st); }
     }
     W = level == 1 ? ws.g1(sp) : ws.gt(sp);
     if (nchunk > 1) pw = (uint8_t*)ws.cv.take(npart * E + 16);
@@ -1936,29 +1949,52 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
   })) return rc;
   kt->decode(s, c->d_params, ct, c->L, ncols, A, nullptr, nullptr);
   HIP_TRY(hipEventRecord(c->ev2, s));
-  LinDigitsArgs da;
-  da.w = w; da.nrows = nrows; da.d = d; da.w_bits = w_bits; da.omega = plan.omega; da.planes = planes;
-  kt->lin_digits(s, da);
-  if (plan.entries) {
-    LinTableArgs ta;
+  if (grp) {
+    GrpCodesArgs ca;
+    ca.w = w; ca.nrows = nrows; ca.d = d; ca.ngroups = gp.ngroups; ca.w_bits = w_bits; ca.g = gp.g;
+    ca.codes = (int16_t*)planes;
+    kt->grp_codes(s, ca);
+    GrpTableArgs ta;
     ta.cx = A.c0; ta.cy = A.c1; ta.cinf = A.inf; ta.sc = A.stride;
     ta.tx = T.c0; ta.ty = T.c1; ta.tinf = T.inf; ta.st = T.stride;
-    ta.tz = tz; ta.tp = tp;
-    ta.ncols = ncols; ta.H = H;
-    kt->lin_table(s, c->d_params, c->d_consts, level, ta);
+    ta.tp = tp; ta.sp = grp_sp;
+    ta.nvec = nvec; ta.d = d; ta.ngroups = gp.ngroups; ta.g = gp.g; ta.M = (int)gp.M;
+    kt->grp_table(s, c->d_params, c->d_consts, level, ta);
+    HIP_TRY(hipEventRecord(c->ev3, s));
+    c->ev2_valid = true;
+    c->aux_kernel = level == 1 ? "k_grp_table_g1" : "k_grp_table_gt";
+    HIP_TRY(hipEventRecord(c->ev0, s));
+    GrpWalkArgs ga;
+    ga.tx = T.c0; ga.ty = T.c1; ga.tinf = T.inf; ga.st = T.stride; ga.M = (int)gp.M;
+    ga.codes = (const int16_t*)planes; ga.w_bits = w_bits;
+    ga.ox = W.c0; ga.oy = W.c1; ga.oinf = W.inf; ga.so = W.stride;
+    ga.nvec = nvec; ga.nrows = nrows; ga.ngroups = gp.ngroups; ga.nchunk = nchunk;
+    kt->grp_walk(s, c->d_params, c->d_consts, level, ga);
   } else {
-    T = A;                             // window width 1: the entries are the elements themselves
+    LinDigitsArgs da;
+    da.w = w; da.nrows = nrows; da.d = d; da.w_bits = w_bits; da.omega = plan.omega; da.planes = planes;
+    kt->lin_digits(s, da);
+    if (plan.entries) {
+      LinTableArgs ta;
+      ta.cx = A.c0; ta.cy = A.c1; ta.cinf = A.inf; ta.sc = A.stride;
+      ta.tx = T.c0; ta.ty = T.c1; ta.tinf = T.inf; ta.st = T.stride;
+      ta.tz = tz; ta.tp = tp;
+      ta.ncols = ncols; ta.H = H;
+      kt->lin_table(s, c->d_params, c->d_consts, level, ta);
+    } else {
+      T = A;                             // window width 1: the entries are the elements themselves
+    }
+    HIP_TRY(hipEventRecord(c->ev3, s));
+    c->ev2_valid = true;
+    c->aux_kernel = !plan.entries ? "k_lin_digits" : level == 1 ? "k_lin_table_g1" : "k_lin_table_gt";
+    HIP_TRY(hipEventRecord(c->ev0, s));
+    LinWalkArgs wa;
+    wa.tx = T.c0; wa.ty = T.c1; wa.tinf = T.inf; wa.st = T.stride; wa.H = H;
+    wa.planes = planes; wa.omega = plan.omega; wa.nwin = plan.nwin;
+    wa.ox = W.c0; wa.oy = W.c1; wa.oinf = W.inf; wa.so = W.stride;
+    wa.nvec = nvec; wa.nrows = nrows; wa.d = d; wa.nchunk = nchunk;
+    kt->lin_walk(s, c->d_params, c->d_consts, level, wa);
   }
-  HIP_TRY(hipEventRecord(c->ev3, s));
-  c->ev2_valid = true;
-  c->aux_kernel = !plan.entries ? "k_lin_digits" : level == 1 ? "k_lin_table_g1" : "k_lin_table_gt";
-  HIP_TRY(hipEventRecord(c->ev0, s));
-  LinWalkArgs wa;
-  wa.tx = T.c0; wa.ty = T.c1; wa.tinf = T.inf; wa.st = T.stride; wa.H = H;
-  wa.planes = planes; wa.omega = plan.omega; wa.nwin = plan.nwin;
-  wa.ox = W.c0; wa.oy = W.c1; wa.oinf = W.inf; wa.so = W.stride;
-  wa.nvec = nvec; wa.nrows = nrows; wa.d = d; wa.nchunk = nchunk;
-  kt->lin_walk(s, c->d_params, c->d_consts, level, wa);
   uint8_t* last = r_be ? res : out;
   kt->encode(s, level == 1 ? W.inf : nullptr, W.c0, W.c1, W.stride, c->L, npart, nchunk > 1 ? pw : last);
   const uint8_t* in = pw;
@@ -1970,7 +2006,7 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
     len = fold.split[k];
   }
   HIP_TRY(hipEventRecord(c->ev1, s));
-  c->last_kernel = level == 1 ? "k_lin_walk_g1" : "k_lin_walk_gt";
+  c->last_kernel = grp ? (level == 1 ? "k_grp_walk_g1" : "k_grp_walk_gt") : (level == 1 ? "k_lin_walk_g1" : "k_lin_walk_gt");
   c->ev_valid = true;
   if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
     kt->decode_plain(s, c->d_params, res, c->L, nout, O);

@@ -250,6 +250,31 @@ struct LinWalkArgs {
   size_t nvec, nrows, d, nchunk;
 };
 
+// The same map by column groups (groupops.hpp), for weights of at most four bits: ngroups = ceil(d / g) groups of g
+// consecutive columns per vector, M = (3^g - 1) / 2 table entries per group.
+// Codes: the balanced-ternary code of bit plane t < w_bits, group G, row r at element (t*ngroups + G)*nrows + r.
+struct GrpCodesArgs {
+  const int32_t* w; size_t nrows, d, ngroups;
+  int w_bits, g;
+  int16_t* codes;
+};
+// Group tables: entry m = 1 .. M of group q = v*ngroups + G at element q*M + (m-1).
+struct GrpTableArgs {
+  const uint32_t* cx; const uint32_t* cy; const uint8_t* cinf; size_t sc;   // the decoded vector(s), canonical Montgomery
+  uint32_t* tx; uint32_t* ty; uint8_t* tinf; size_t st;                     // entries, canonical Montgomery (tinf: level 1)
+  uint32_t* tp; size_t sp;                                                  // level 1: prefix products, 3^(g-1) per lane launched
+  size_t nvec, d, ngroups;
+  int g, M;
+};
+// The walk: lane (v*nchunk + c)*nrows + r sums the groups of chunk c for output (v, r) into element
+// (v*nrows + r)*nchunk + c of the output.
+struct GrpWalkArgs {
+  const uint32_t* tx; const uint32_t* ty; const uint8_t* tinf; size_t st; int M;
+  const int16_t* codes; int w_bits;
+  uint32_t* ox; uint32_t* oy; uint8_t* oinf; size_t so;                     // plain canonical out
+  size_t nvec, nrows, ngroups, nchunk;
+};
+
 // Sparse linear maps (sparseops.hpp): out[v][r] = sum_{e in row r} w[e] * ct[v][col[e]] over a compressed-row structure.
 // Digit planes: window t of w[e] at element t*nnz_pad + e (int8; int16 at omega = 8); zero where col[e] >= d.
 struct SpDigitsArgs {
@@ -460,9 +485,13 @@ struct KernelTable {
   void (*bkt_scatter)(hipStream_t s, BktSortArgs a);
   void (*bkt_reduce)(hipStream_t s, const void* params, const PairingConsts* consts, int level, BktReduceArgs a);
   void (*bkt_fold)(hipStream_t s, const void* params, const PairingConsts* consts, int level, BktFoldArgs a);
+  // the dense linear map by column groups (groupops.hpp): the codes of the weights, the group tables, the walk
+  void (*grp_codes)(hipStream_t s, GrpCodesArgs a);
+  void (*grp_table)(hipStream_t s, const void* params, const PairingConsts* consts, int level, GrpTableArgs a);
+  void (*grp_walk)(hipStream_t s, const void* params, const PairingConsts* consts, int level, GrpWalkArgs a);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
-  Entry entries[32];
+  Entry entries[40];
 };
 
 const KernelTable* kernel_table_nl3();

@@ -1388,6 +1388,13 @@ static void launch_lin_walk(hipStream_t s, const void* params, const PairingCons
                        consts, a);
 }
 
+// ---- the dense linear map by column groups (groupops.hpp) ---------------------------------------------------------
+// The kernels and launchers live in units of their own (group_impl.hpp, kern_grp_nl*.hip).
+void BGN_CAT(launch_grp_codes_nl, BGN_NL)(hipStream_t s, GrpCodesArgs a);
+void BGN_CAT(launch_grp_table_nl, BGN_NL)(hipStream_t s, const void* params, const PairingConsts* consts, int level, GrpTableArgs a);
+void BGN_CAT(launch_grp_walk_nl, BGN_NL)(hipStream_t s, const void* params, const PairingConsts* consts, int level, GrpWalkArgs a);
+const void* BGN_CAT(grp_kernel_nl, BGN_NL)(int which);
+
 // ---- sparse linear maps (sparseops.hpp) --------------------------------------------------------------------------
 template <int NL>
 __global__ void __launch_bounds__(FP_BLOCK)
@@ -1846,6 +1853,9 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
       launch_bkt_scatter,
       launch_bkt_reduce,
       launch_bkt_fold,
+      BGN_CAT(launch_grp_codes_nl, BGN_NL),
+      BGN_CAT(launch_grp_table_nl, BGN_NL),
+      BGN_CAT(launch_grp_walk_nl, BGN_NL),
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1883,6 +1893,10 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
        {"k_bkt_reduce_gt", (const void*)k_bkt_reduce<NL_, 2>},
        {"k_bkt_fold_g1", (const void*)k_bkt_fold<NL_, 1>},
        {"k_bkt_fold_gt", (const void*)k_bkt_fold<NL_, 2>},
+       {"k_grp_walk_g1", BGN_CAT(grp_kernel_nl, BGN_NL)(0)},
+       {"k_grp_walk_gt", BGN_CAT(grp_kernel_nl, BGN_NL)(1)},
+       {"k_grp_table_g1", BGN_CAT(grp_kernel_nl, BGN_NL)(2)},
+       {"k_grp_table_gt", BGN_CAT(grp_kernel_nl, BGN_NL)(3)},
        {nullptr, nullptr}},
   };
   return &t;

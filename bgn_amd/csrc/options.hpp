@@ -71,6 +71,8 @@ struct Options {
                            // plan_lincomb_buckets: long vectors under few rows), 0 never, 1 always — same bytes
   V lin_bucket_window{-1}; // ... its window width, 1 .. 8 (-1: planned)
   V lin_bucket_run{-1};    // ... and the entries of a bucket one lane of a reduce pass sums, 2 .. 256 (-1: planned)
+  V lin_groups{-1};        // linear maps of narrow weights (w_bits <= 4) by column groups (groupops.hpp): -1 planned (dispatch.hpp
+                           // plan_lincomb_groups), 0 never, 2 .. 6 that group size, narrowed until the tables fit — same bytes
   V poly_karatsuba{1};    // Karatsuba levels on square MultPoly products
   V poly_levels{-1};       // forced number of levels (-1: planned)
   V poly_tables{-1};       // per-coefficient line tables: 0 never, 1 always, -1 by size
@@ -149,6 +151,7 @@ inline const OptionDesc* option_table(size_t* n) {
       {"lin_buckets", &Options::lin_buckets, true, nullptr},
       {"lin_bucket_window", &Options::lin_bucket_window, true, nullptr},
       {"lin_bucket_run", &Options::lin_bucket_run, true, nullptr},
+      {"lin_groups", &Options::lin_groups, true, nullptr},
       {"poly_karatsuba", &Options::poly_karatsuba, true, nullptr},
       {"poly_levels", &Options::poly_levels, true, nullptr},
       {"poly_tables", &Options::poly_tables, true, nullptr},

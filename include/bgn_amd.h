@@ -273,6 +273,12 @@ int bgn_sum_batch(bgn_ctx* ctx, size_t nseg, size_t seg_len, int level, const ui
  * buckets summed in runs and folded, no table built; planned by dispatch.hpp plan_lincomb_buckets, never below 1024
  * columns; options lin_buckets (-1 planned, 0 never, 1 always), lin_bucket_window (1 .. 8), lin_bucket_run (2 .. 256).
  * Where its workspace does not fit the context's memory budget the table path serves.
+ * A third path, again with identical bytes, serves many rows of NARROW weights (w_bits <= 4: selection and membership
+ * masks, bit databases, binarised or 2 .. 4-bit layers), where a table per ciphertext saves nothing: groups of g
+ * consecutive ciphertexts share one table of all their signed combinations ((3^g - 1) / 2 entries), and an output costs
+ * one addition per group and bit plane instead of one per column (csrc/groupops.hpp; planned by dispatch.hpp
+ * plan_lincomb_groups; option lin_groups: -1 planned, 0 never, 2 .. 6 that group size, narrowed until the tables fit the
+ * memory budget; lin_split counts chunks of whole groups there, lin_window does not apply).
  * Replaces the loops of MultConst (bgn.go:253-291) and Add (bgn.go:442-497) a weighted sum, a linear layer, EvalPoly or
  * MultConstPoly is computed with. */
 int bgn_lincomb_batch(bgn_ctx* ctx, size_t nvec, size_t nrows, size_t d, int level, const uint8_t* ct, const int32_t* w,
