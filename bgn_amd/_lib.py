@@ -41,6 +41,8 @@ PROTOTYPES = {
     "bgn_add_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p]),
     "bgn_sub_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p]),
     "bgn_neg_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p]),
+    "bgn_compress_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p]),
+    "bgn_decompress_batch": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p]),
     "bgn_sum_batch": (C.c_int, [_ctx, _sz, _sz, C.c_int, _u8p, _u8p, _sz, _u8p]),
     "bgn_lincomb_batch": (C.c_int, [_ctx, _sz, _sz, _sz, C.c_int, _u8p, _u8p, C.c_int, _u8p, _sz, _u8p]),
     "bgn_sparse_lincomb_batch": (C.c_int, [_ctx, _sz, _sz, _sz, _sz, _sz, C.c_int, _u8p, _u8p, _u8p, _u8p, C.c_int, _u8p, _sz,
@@ -72,6 +74,8 @@ PROTOTYPES = {
     "bgn_add_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_sub_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_neg_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, C.c_void_p]),
+    "bgn_compress_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, C.c_void_p]),
+    "bgn_decompress_batch_dev": (C.c_int, [_ctx, _sz, C.c_int, _u8p, _u8p, _u8p, C.c_void_p]),
     "bgn_sum_batch_dev": (C.c_int, [_ctx, _sz, _sz, C.c_int, _u8p, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_lincomb_batch_dev": (C.c_int, [_ctx, _sz, _sz, _sz, C.c_int, _u8p, _u8p, C.c_int, _u8p, _sz, _u8p, C.c_void_p]),
     "bgn_sparse_lincomb_batch_dev": (C.c_int, [_ctx, _sz, _sz, _sz, _sz, _sz, C.c_int, _u8p, _u8p, _u8p, _u8p, C.c_int, _u8p,

@@ -128,6 +128,23 @@ class Engine:
         check(self._lib.bgn_neg_batch(self._h, len(A), level, _ptr(A), _ptr(out)), "bgn_neg_batch")
         return out
 
+    def compress(self, level: int, a: BytesLike) -> np.ndarray:
+        """The compressed wire form (bgn_compress_batch): fp_bytes + 1 bytes per element, x (level 1) or re (level 2)
+        and one flag byte.  Level 2 is exact only for norm-1 elements."""
+        A = _as_u8(a, self.elem_bytes)
+        out = np.zeros((len(A), self.L + 1), dtype=np.uint8)
+        check(self._lib.bgn_compress_batch(self._h, len(A), level, _ptr(A), _ptr(out)), "bgn_compress_batch")
+        return out
+
+    def decompress(self, level: int, a: BytesLike):
+        """(full elements, ok) of compressed elements (bgn_decompress_batch): a rejected element (ok 0) comes back as
+        the level's identity encoding; an accepted level-1 element lies on the curve by construction."""
+        A = _as_u8(a, self.L + 1)
+        out = self._out(len(A))
+        ok = np.zeros(len(A), dtype=np.uint8)
+        check(self._lib.bgn_decompress_batch(self._h, len(A), level, _ptr(A), _ptr(out), _ptr(ok)), "bgn_decompress_batch")
+        return out, ok
+
     def sum(self, level: int, ct: BytesLike, seg_len: int, r=None) -> np.ndarray:
         """Segmented sum (bgn_sum_batch): `ct` holds nseg * seg_len elements row-major, row s of the result is the
         sum of segment s (level 1: G1 addition, level 2: the GT product), blinded with one r per segment if given."""
@@ -366,6 +383,23 @@ class Engine:
         self._need("out", out, count * self.elem_bytes)
         check(self._lib.bgn_neg_batch_dev(self._h, count, level, a.data_ptr(), out.data_ptr(), self._stream()),
               "bgn_neg_batch_dev")
+
+    def compress_dev(self, level: int, a, out, count: int) -> None:
+        """Device-resident bgn_compress_batch_dev: `a` holds count full elements, `out` takes count * (fp_bytes + 1)
+        bytes.  Arrays at any byte address; `out` must not overlap `a`."""
+        self._need("a", a, count * self.elem_bytes)
+        self._need("out", out, count * (self.L + 1))
+        check(self._lib.bgn_compress_batch_dev(self._h, count, level, a.data_ptr(), out.data_ptr(), self._stream()),
+              "bgn_compress_batch_dev")
+
+    def decompress_dev(self, level: int, a, out, ok, count: int) -> None:
+        """Device-resident bgn_decompress_batch_dev: `a` holds count * (fp_bytes + 1) bytes, `out` takes count full
+        elements and `ok` count bytes.  Arrays at any byte address; `out` must not overlap `a`."""
+        self._need("a", a, count * (self.L + 1))
+        self._need("out", out, count * self.elem_bytes)
+        self._need("ok", ok, count)
+        check(self._lib.bgn_decompress_batch_dev(self._h, count, level, a.data_ptr(), out.data_ptr(), ok.data_ptr(),
+                                                 self._stream()), "bgn_decompress_batch_dev")
 
     def sum_dev(self, level: int, ct, out, nseg: int, seg_len: int, r=None, r_len: int = 0) -> None:
         """Device-resident segmented sum (bgn_sum_batch_dev): ct holds nseg * seg_len elements, out nseg; r (nseg x

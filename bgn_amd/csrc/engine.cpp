@@ -33,6 +33,7 @@ int ensure_arena(bgn_ctx* c, size_t bytes);      // (carve.hpp grows the workspa
 }
 #include "carve.hpp"
 #include "linrecode.hpp"
+#include "sqrtrecode.hpp"
 
 using namespace bgn;
 
@@ -145,6 +146,9 @@ struct bgn_ctx {
   // Mult on the a = -3 curve (pairing.hpp miller_double): u^2 R^2 | u^3 R^2 mod p, 2 * nl tight limbs — the factors
   // k_decode multiplies x and y by instead of R^2.  Null: p has no fourth root of -3, the route is off for this key.
   uint32_t* d_a3 = nullptr;
+  // the square root's exponent (p + 1) / 4 as the program of sqrtrecode.hpp: what k_decompress walks
+  uint16_t* d_sqrt_ops = nullptr;
+  int sqrt_nops = 0;
   int pair_ws_slots = 3;               // F_p values of pairing workspace per pairing: 3 + the windowed loop's table
   // decryption lift over the secret order (set_secret): line table of f_{q2, q1*P} and the constants whose
   // NAF is that of q2 = n / q1 — half the Miller steps of e(P, .)
@@ -482,6 +486,7 @@ void bgn_ctx_destroy(bgn_ctx* c) {
   if (c->d_params_n) (void)ctx_free(c, c->d_params_n);
   if (c->rand_ws) (void)ctx_wipe_free(c, c->rand_ws);
   if (c->d_consts) (void)ctx_free(c, c->d_consts);
+  if (c->d_sqrt_ops) (void)ctx_free(c, c->d_sqrt_ops);
   if (c->d_a3) (void)ctx_free(c, c->d_a3);
   if (c->d_keypts) (void)ctx_free(c, c->d_keypts);
   if (c->d_keywire) (void)ctx_free(c, c->d_keywire);
@@ -610,6 +615,16 @@ int bgn_ctx_create(bgn_ctx** out, const uint8_t* p_be, size_t p_len, const uint8
     HIP_BRK(ctx_malloc(c, (void**)&c->d_consts, sizeof pc));
     HIP_BRK(hipMemcpy(c->d_consts, &pc, sizeof pc, hipMemcpyHostToDevice));
     c->pc_host = pc;
+    {
+      // root = rhs^((p + 1) / 4) needs p = 3 mod 4, checked above; the exponent is public and recoded once
+      BigU e = p1;
+      e.shr1();
+      e.shr1();
+      const std::vector<uint16_t> ops = sqrt_recode(e.w.data(), e.bits());
+      c->sqrt_nops = (int)ops.size();
+      HIP_BRK(ctx_malloc(c, (void**)&c->d_sqrt_ops, ops.size() * sizeof(uint16_t)));
+      HIP_BRK(hipMemcpy(c->d_sqrt_ops, ops.data(), ops.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
     {
       // the decode factors of the a = -3 route (hostbig.hpp curve_a3_root): (x, y) -> (u^2 x, u^3 y), u^4 = -3
       BigU u;
@@ -2320,6 +2335,51 @@ int bgn_neg_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, uin
   return BGN_OK;
 }
 
+// ---- the compressed wire form ------------------------------------------------------------------------------------
+// L + 1 bytes per element (include/bgn_amd.h): one launch each way, no workspace, lane kernels only (compressops.hpp).
+namespace {
+int compress_check(const bgn_ctx* c, size_t count, int level, const void* in, const void* out, const void* ok, bool with_ok) {
+  if (!c) return fail(BGN_E_ARG, "null argument");
+  if (level != 1 && level != 2) return fail(BGN_E_ARG, "level must be 1 or 2");
+  if (!count) return BGN_OK;
+  if (!in || !out || (with_ok && !ok)) return fail(BGN_E_ARG, "null argument");
+  if (count > kMaxBatch) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
+  return BGN_OK;
+}
+}  // namespace
+
+int bgn_compress_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* in, uint8_t* out, void* stream) {
+  if (int rc = compress_check(c, count, level, in, out, nullptr, false)) return rc;
+  if (!count) return BGN_OK;
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  c->kt->compress_wire(s, c->d_params, in, c->L, count, level, out);
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->last_kernel = "k_compress_wire";
+  c->ev_valid = true;
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+
+int bgn_decompress_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* in, uint8_t* out, uint8_t* ok, void* stream) {
+  if (int rc = compress_check(c, count, level, in, out, ok, true)) return rc;
+  if (!count) return BGN_OK;
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lk(c->mu);
+  StreamOrder order(c, s);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipEventRecord(c->ev0, s));
+  c->kt->decompress(s, c->d_params, c->d_sqrt_ops, c->sqrt_nops, in, c->L, count, level, out, ok);
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->last_kernel = "k_decompress";
+  c->ev_valid = true;
+  HIP_TRY(hipGetLastError());
+  return BGN_OK;
+}
+
 int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint8_t* k_be, size_t k_len,
                             const uint8_t* r_be, size_t r_len, uint8_t* out, void* stream) {
   if (!c || (count && (!a || !k_be || !out))) return fail(BGN_E_ARG, "null argument");
@@ -3024,6 +3084,27 @@ int bgn_neg_batch(bgn_ctx* c, size_t count, int level, const uint8_t* a, uint8_t
   if (!count) return BGN_OK;
   const size_t E = 2 * (size_t)c->L;
   return host_call(c, COMB_NEG, level, {{a, nullptr, E, count}, {nullptr, out, E, count}});
+}
+
+// The compressed form: rows of two sizes, no CombineOp; the _dev entry points are the device side.
+int bgn_compress_batch(bgn_ctx* c, size_t count, int level, const uint8_t* in, uint8_t* out) {
+  if (int rc = compress_check(c, count, level, in, out, nullptr, false)) return rc;
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L, CE = (size_t)c->L + 1;
+  return host_call(c, 0, 0, {{in, nullptr, E, count}, {nullptr, out, CE, count}},
+                   [&](size_t n, uint8_t* const* i, uint8_t* const* o, hipStream_t s) {
+                     return bgn_compress_batch_dev(c, n, level, i[0], o[0], s);
+                   });
+}
+
+int bgn_decompress_batch(bgn_ctx* c, size_t count, int level, const uint8_t* in, uint8_t* out, uint8_t* ok) {
+  if (int rc = compress_check(c, count, level, in, out, ok, true)) return rc;
+  if (!count) return BGN_OK;
+  const size_t E = 2 * (size_t)c->L, CE = (size_t)c->L + 1;
+  return host_call(c, 0, 0, {{in, nullptr, CE, count}, {nullptr, out, E, count}, {nullptr, ok, 1, count}},
+                   [&](size_t n, uint8_t* const* i, uint8_t* const* o, hipStream_t s) {
+                     return bgn_decompress_batch_dev(c, n, level, i[0], o[0], o[1], s);
+                   });
 }
 
 // The rows of `ct` are whole segments, not elements: no CombineOp, the _dev entry point is the device side.

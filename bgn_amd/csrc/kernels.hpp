@@ -489,6 +489,12 @@ struct KernelTable {
   void (*grp_codes)(hipStream_t s, GrpCodesArgs a);
   void (*grp_table)(hipStream_t s, const void* params, const PairingConsts* consts, int level, GrpTableArgs a);
   void (*grp_walk)(hipStream_t s, const void* params, const PairingConsts* consts, int level, GrpWalkArgs a);
+  // the compressed wire form (compressops.hpp; L + 1 bytes per element, include/bgn_amd.h), arrays at any byte address,
+  // out never overlapping in.  compress_wire: full -> compressed, one launch, no field product.  decompress:
+  // compressed -> full canonical bytes and ok[e]; ops / nops: the device copy of sqrt_recode((p + 1) / 4).
+  void (*compress_wire)(hipStream_t s, const void* params, const uint8_t* in, int L, size_t count, int level, uint8_t* out);
+  void (*decompress)(hipStream_t s, const void* params, const uint16_t* ops, int nops, const uint8_t* in, int L, size_t count,
+                     int level, uint8_t* out, uint8_t* ok);
   // host-side handles of the lane kernels by the name bgn_last_kernel_name reports (the same query); null-terminated
   struct Entry { const char* name; const void* fn; };
   Entry entries[40];

@@ -16,6 +16,7 @@
 #include "linops.hpp"
 #include "sparseops.hpp"
 #include "bucketops.hpp"
+#include "compressops.hpp"
 
 namespace bgn {
 
@@ -1790,6 +1791,20 @@ static void launch_random_scalars(hipStream_t s, const void* params_n, RandSeed 
                      (u64)stream_id, (u64)first_index, count, (int)n_len, out);
 }
 
+static void launch_compress_wire(hipStream_t s, const void* params, const uint8_t* in, int L, size_t count, int level,
+                                 uint8_t* out) {
+  if (!count) return;
+  hipLaunchKernelGGL(k_compress_wire<NL_>, dim3(grid_for(count)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params, in, L,
+                     count, level, out);
+}
+
+static void launch_decompress(hipStream_t s, const void* params, const uint16_t* ops, int nops, const uint8_t* in, int L,
+                              size_t count, int level, uint8_t* out, uint8_t* ok) {
+  if (!count || nops < 1) return;
+  hipLaunchKernelGGL(k_decompress<NL_>, dim3(grid_for(count)), dim3(FP_BLOCK), 0, s, (const FpParams<NL_>*)params, ops, nops,
+                     in, L, count, level, out, ok);
+}
+
 const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
   static const KernelTable t = {
       NL_,
@@ -1856,6 +1871,8 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
       BGN_CAT(launch_grp_codes_nl, BGN_NL),
       BGN_CAT(launch_grp_table_nl, BGN_NL),
       BGN_CAT(launch_grp_walk_nl, BGN_NL),
+      launch_compress_wire,
+      launch_decompress,
       {{"k_pairing<" BGN_STR(BGN_NL) ", 0>", (const void*)k_pairing<NL_, 0>},
        {"k_pairing<" BGN_STR(BGN_NL) ", 1>", (const void*)k_pairing<NL_, 1>},
        {"k_g1_add_wire", (const void*)k_g1_add_wire<NL_>},
@@ -1897,6 +1914,8 @@ const KernelTable* BGN_CAT(kernel_table_nl, BGN_NL)() {
        {"k_grp_walk_gt", BGN_CAT(grp_kernel_nl, BGN_NL)(1)},
        {"k_grp_table_g1", BGN_CAT(grp_kernel_nl, BGN_NL)(2)},
        {"k_grp_table_gt", BGN_CAT(grp_kernel_nl, BGN_NL)(3)},
+       {"k_compress_wire", (const void*)k_compress_wire<NL_>},
+       {"k_decompress", (const void*)k_decompress<NL_>},
        {nullptr, nullptr}},
   };
   return &t;

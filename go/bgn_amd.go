@@ -451,6 +451,35 @@ func (e *Engine) NegBatch(a []*Ciphertext, l2 bool) ([]*Ciphertext, error) {
 	return e.unpack(out, l2), nil
 }
 
+// CompressBatch writes the compressed wire form of a (bgn_compress_batch): e.L+1 bytes per element, x (level 1) or re
+// (level 2) and one flag byte.  Level 2 is exact only for norm-1 elements.
+func (e *Engine) CompressBatch(a []*Ciphertext, l2 bool) ([]byte, error) {
+	A := e.pack(a)
+	out := make([]byte, len(a)*(e.L+1))
+	if err := locked(func() C.int { return C.bgn_compress_batch(e.h, C.size_t(len(a)), levelOf(l2), u8(A), u8(out)) }); err != nil {
+		return nil, err
+	}
+	return out, nil
+}
+
+// DecompressBatch expands len(compressed)/(e.L+1) compressed elements (bgn_decompress_batch).  ok[i] == 0 marks a
+// rejected element, which comes back as the level's identity; an accepted level-1 element lies on the curve.
+func (e *Engine) DecompressBatch(compressed []byte, l2 bool) ([]*Ciphertext, []byte, error) {
+	if len(compressed)%(e.L+1) != 0 {
+		return nil, nil, errors.New("bgn_amd: the length is not a multiple of the compressed element size")
+	}
+	count := len(compressed) / (e.L + 1)
+	out := make([]byte, count*2*e.L)
+	ok := make([]byte, count)
+	err := locked(func() C.int {
+		return C.bgn_decompress_batch(e.h, C.size_t(count), levelOf(l2), u8(compressed), u8(out), u8(ok))
+	})
+	if err != nil {
+		return nil, nil, err
+	}
+	return e.unpack(out, l2), ok, nil
+}
+
 // MultBatch is pk.Mult (bgn.go:294-314) over arrays.  In non-deterministic mode the caller-supplied randomness
 // r[i] < N replaces newCryptoRandom (bgn.go:303).
 func (e *Engine) MultBatch(a, b []*Ciphertext, r []*big.Int) ([]*Ciphertext, error) {
@@ -1156,6 +1185,43 @@ func (e *Engine) NegBatchDev(a *DeviceArray) (*DeviceArray, error) {
 		return nil, err
 	}
 	return out, nil
+}
+
+// CompressBatchDev is CompressBatch over a device array (bgn_compress_batch_dev): rows of e.L+1 bytes, left on the device.
+func (e *Engine) CompressBatchDev(a *DeviceArray) (*DeviceArray, error) {
+	out, err := e.NewDeviceArray(a.Count, e.L+1, a.L2)
+	if err != nil {
+		return nil, err
+	}
+	err = locked(func() C.int { return C.bgn_compress_batch_dev(e.h, C.size_t(a.Count), levelOf(a.L2), a.u8(), out.u8(), nil) })
+	if err != nil {
+		out.Free()
+		return nil, err
+	}
+	return out, nil
+}
+
+// DecompressBatchDev is DecompressBatch over a device array of compressed rows (bgn_decompress_batch_dev): the full
+// elements and the ok bytes stay on the device.
+func (e *Engine) DecompressBatchDev(compressed *DeviceArray) (*DeviceArray, *DeviceArray, error) {
+	out, err := e.likeOut(compressed.Count, compressed.L2)
+	if err != nil {
+		return nil, nil, err
+	}
+	ok, err := e.NewDeviceArray(compressed.Count, 1, false)
+	if err != nil {
+		out.Free()
+		return nil, nil, err
+	}
+	err = locked(func() C.int {
+		return C.bgn_decompress_batch_dev(e.h, C.size_t(compressed.Count), levelOf(compressed.L2), compressed.u8(), out.u8(), ok.u8(), nil)
+	})
+	if err != nil {
+		out.Free()
+		ok.Free()
+		return nil, nil, err
+	}
+	return out, ok, nil
 }
 
 // MultBatchDev is pk.Mult over device arrays of level-1 ciphertexts (bgn.go:294-314; bgn_mult_batch_dev).

@@ -393,6 +393,39 @@ int bgn_poly_eval_batch(bgn_ctx* ctx, size_t npoly, size_t d, int level, const u
  * ciphertexts from an untrusted source go through this call first. */
 int bgn_validate_batch(bgn_ctx* ctx, size_t count, int level, const uint8_t* in, uint8_t* ok);
 
+/* The compressed wire form: half the bytes of a ciphertext array.  This project's own form, not pinned to PBC's
+ * compressed element bytes (nothing here is pinned to PBC: PBC is not in the tree).
+ * An element is fp_bytes + 1 bytes: fp_bytes of big-endian x (level 1) or re (level 2), canonical (< p), then one flag
+ * byte.
+ *   level 1: the identity (all zero in full form) is x = 0 with flag 0x00; a finite point (x, y) has flag
+ *            0x02 | (y & 1) on the canonical residue y (p is odd: y and p - y differ in parity unless y = 0).
+ *   level 2: flag 0x02 | (im & 1); 1 || 0 is re = 1 with flag 0x02, no special case.
+ * bgn_compress_batch: in = count full elements, out = count compressed ones.  Level 2 reduces residues >= p first, as
+ * Add does.  It checks nothing: level 1 takes valid points or the identity; level 2 is exact only for norm-1 inputs
+ * (re^2 + im^2 = 1, what bgn_validate_batch accepts) — for any other input decompress(compress(z)) is some norm-1
+ * element or a rejection.
+ * bgn_decompress_batch: in = count compressed elements, out = count full elements in canonical wire bytes, ok[i] = 1
+ * for an accepted element.  ok[i] = 0 and out[i] = the level's identity encoding (level 1 all zero, level 2 1 || 0)
+ * when the flag is not one of 0x00, 0x02, 0x03; the flag is 0x00 on level 2, or on level 1 with x != 0; x >= p;
+ * rhs = x^3 + x (level 1) or 1 - re^2 (level 2) is not a square (the test is root^2 != rhs); the root is 0 and the
+ * flag is 0x03; or, level 1, x = 0 with flag 0x02: (0, 0) has the identity's full-form bytes, so the all-zero
+ * compressed form is the only accepted spelling of that element and compress after decompress is the identity on
+ * accepted inputs.  The root written is the one whose canonical parity is the flag's low bit.  A level-1 element
+ * rebuilt from x lies on the curve by construction: decompressing an untrusted batch is also its curve check (not a
+ * subgroup check, as bgn_validate_batch is none).
+ * count == 0 is BGN_OK; a null context (refused first), a level other than 1 or 2, a null pointer or count above 2^28
+ * is BGN_E_ARG before any device work.  out must not overlap in (the element sizes differ).  The device forms are
+ * stream-ordered, read nothing back and take arrays at any byte address.  Neither form joins the combiner of
+ * concurrent small calls.  One launch each on the lane kernels (csrc/compressops.hpp): k_compress_wire has no field
+ * product and is bound by memory; k_decompress computes rhs^((p+1)/4) per lane — about 1030 squarings and 260 products
+ * at a 1024-bit key under the key's public exponent, recoded once per context — so ONE element costs what a full batch
+ * of 65 536 costs: the latency of that chain (there is no cooperative or lane-group variant for small batches).
+ * 2^20 device-resident elements of a 1024-bit key (profiles/r16_compress_rates.csv): compress 1.4 x 10^10 /s (0.70 of the
+ * HBM peak on its 388 bytes per element; Neg in the same run 0.69 on 516), decompress 8.2 x 10^6 /s on either level —
+ * 12 x MultConst level 1 with 1024-bit scalars, 0.91 of the one-wave multiply-add ceiling, no scratch; one element: 8 ms. */
+int bgn_compress_batch(bgn_ctx* ctx, size_t count, int level, const uint8_t* in, uint8_t* out);
+int bgn_decompress_batch(bgn_ctx* ctx, size_t count, int level, const uint8_t* in, uint8_t* out, uint8_t* ok);
+
 /* ok[i] = 1 iff ct[i] == P^v[i] * Q^r[i] (Element.Equals on the affine point).  v, r: any non-negative
  * integers (sums of plaintexts / randomness exceed n, gadgets_test.go:37-39).
  * Replaces CheckDecryptionProof (gadgets.go:57-61). */
@@ -476,6 +509,9 @@ int bgn_poly_eval_batch_dev(bgn_ctx* ctx, size_t npoly, size_t d, int level, con
                             uint8_t* out, void* stream);
 
 int bgn_validate_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* in, uint8_t* ok, void* stream);
+int bgn_compress_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* in, uint8_t* out, void* stream);
+int bgn_decompress_batch_dev(bgn_ctx* ctx, size_t count, int level, const uint8_t* in, uint8_t* out, uint8_t* ok,
+                             void* stream);
 /* The proof checks, Prove and Verify synchronise the stream before returning (they own scratch buffers);
  * bgn_check_plaintext_knowledge_batch_dev takes challenges the caller computed, bgn_verify_plaintext_knowledge_batch_dev
  * computes them from the device-resident proof. */
@@ -632,7 +668,7 @@ double bgn_last_aux_kernel_ms(bgn_ctx* ctx);
 const char* bgn_last_aux_kernel_name(bgn_ctx* ctx);
 /* What the code object says about the kernel bgn_last_kernel_name names, when the engine knows its entry point
  * (the lane kernels: k_pairing<NL, 0|1>, k_g1_add_wire, k_gt_mul_wire, k_neg_wire, k_g1_add, k_gt_mul, k_g1_mul,
- * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response, k_random_scalars, k_sum_g1_wire, k_sum_gt_wire, k_lin_walk_g1, k_lin_walk_gt): out[0] = vector registers per lane, out[1] = scratch
+ * k_gt_pow, k_g1_fixed_chain, k_challenge, k_pok_response, k_random_scalars, k_sum_g1_wire, k_sum_gt_wire, k_lin_walk_g1, k_lin_walk_gt, k_compress_wire, k_decompress): out[0] = vector registers per lane, out[1] = scratch
  * (private-segment) bytes per lane, out[2] = static LDS bytes per workgroup, out[3] = threads per workgroup the
  * kernel may be launched with.  A kernel that is meant to hold everything in registers and has started to spill
  * shows here before it shows on a clock.  Returns BGN_E_ARG for a kernel it has no entry point of. */

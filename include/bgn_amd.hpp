@@ -503,6 +503,21 @@ class PublicKey {
           "bgn_sparse_lincomb_batch");
     return split(out, level == 2);
   }
+  // The compressed wire form (bgn_compress_batch / bgn_decompress_batch): a.size() rows of fp_bytes + 1 bytes, x or re
+  // and a flag byte; Decompress returns the full elements (a rejected one as the level's identity) and fills ok.
+  Bytes CompressBatch(const std::vector<Ciphertext>& a) const {
+    const int level = a.empty() || !a[0].L2 ? 1 : 2;
+    Bytes A = join(a), out(a.size() * (E_ / 2 + 1));
+    check(bgn_compress_batch(h_, a.size(), level, A.data(), out.data()), "bgn_compress_batch");
+    return out;
+  }
+  std::vector<Ciphertext> DecompressBatch(const Bytes& compressed, bool l2, Bytes& ok) const {
+    const size_t count = compressed.size() / (E_ / 2 + 1);
+    Bytes out(count * E_);
+    ok.assign(count, 0);
+    check(bgn_decompress_batch(h_, count, l2 ? 2 : 1, compressed.data(), out.data(), ok.data()), "bgn_decompress_batch");
+    return split(out, l2);
+  }
   // Prefix sums (bgn_scan_batch): the running sums of every segment of seg_len consecutive elements — the chain of
   // Add (bgn.go:442-497) a running total is computed with; r: one blinding scalar per output.
   std::vector<Ciphertext> ScanBatch(const std::vector<Ciphertext>& a, size_t seg_len, const std::vector<Scalar>* r = nullptr) const {
@@ -609,6 +624,19 @@ class PublicKey {
     if (r) dr = scalars_dev(*r, rl);
     check(bgn_scan_batch_dev(h_, a.Count / seg_len, seg_len, a.L2 ? 2 : 1, a.data(), r ? dr.data() : nullptr, rl, out.data(), nullptr),
           "bgn_scan_batch_dev");
+    return out;
+  }
+  // bgn_compress_batch_dev / bgn_decompress_batch_dev: the compressed array has rows of fp_bytes + 1 bytes.
+  DeviceArray CompressBatchDev(const DeviceArray& a) const {
+    DeviceArray out(h_, a.Count, E_ / 2 + 1, a.L2);
+    check(bgn_compress_batch_dev(h_, a.Count, a.L2 ? 2 : 1, a.data(), out.data(), nullptr), "bgn_compress_batch_dev");
+    return out;
+  }
+  DeviceArray DecompressBatchDev(const DeviceArray& compressed, DeviceArray& ok) const {
+    DeviceArray out(h_, compressed.Count, E_, compressed.L2);
+    ok = DeviceArray(h_, compressed.Count, 1, false);
+    check(bgn_decompress_batch_dev(h_, compressed.Count, compressed.L2 ? 2 : 1, compressed.data(), out.data(), ok.data(), nullptr),
+          "bgn_decompress_batch_dev");
     return out;
   }
   DeviceArray NegBatchDev(const DeviceArray& a) const {
