@@ -36,6 +36,7 @@ struct Ws {   // the arrays of one call, by kind, for a field of nl limbs
   Ws(int nl_, uint8_t* base) : nl(nl_), cv(base) {}
   SoA2 g1(size_t stride) { return cv.soa(nl, stride, true); }
   SoA2 gt(size_t stride) { return cv.soa(nl, stride, false); }
+  SoA2 elems(int level, size_t stride) { return level == 1 ? g1(stride) : gt(stride); }   // ciphertexts of a level
   uint32_t* fp(size_t stride) { return (uint32_t*)cv.take((size_t)nl * stride * 4); }};
 
 // layout(Ws&) runs twice: against null to size, then, after ensure_arena, against the arena.  It must take the same

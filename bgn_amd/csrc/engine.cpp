@@ -972,7 +972,8 @@ int bgn_ctx_setup_decryption(bgn_ctx* c, uint64_t msg_space) {
 // ---- Mult / makeL2 / MultPoly -------------------------------------------------------
 
 namespace {
-void blind_l2(bgn_ctx* c, hipStream_t s, SoA2 R, const uint8_t* r_be, size_t r_len, SoA2 T1, SoA2 T2, size_t count);
+void blind_encode(bgn_ctx* c, hipStream_t s, int level, SoA2 O, const uint8_t* r_be, size_t r_len, SoA2 T1, SoA2 T2,
+                  uint32_t* prefix, size_t n, uint8_t* out);
 int ensure_gt_table(bgn_ctx* c);
 }
 
@@ -1087,8 +1088,7 @@ static int pairing_chunk(bgn_ctx* c, size_t count, const uint8_t* a, size_t na, 
     HIP_TRY(hipEventRecord(c->ev1, s));
     c->ev_valid = true;
   }
-  if (r_be) blind_l2(c, s, O, r_be, r_len, T1, T2, count);      // res.Mul(res, e(Q,Q)^r), bgn.go:302-311
-  kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, count, out);
+  blind_encode(c, s, 2, O, r_be, r_len, T1, T2, nullptr, count, out);      // res.Mul(res, e(Q,Q)^r), bgn.go:302-311
   HIP_TRY(hipGetLastError());
   return BGN_OK;
 }
@@ -1601,6 +1601,50 @@ void blind_l2(bgn_ctx* c, hipStream_t s, SoA2 R, const uint8_t* r_be, size_t r_l
   (void)hipMemcpyAsync(R.c1, T2.c1, (size_t)c->nl * R.stride * 4, hipMemcpyDeviceToDevice, s);
 }
 
+// The blinding base tables of a call's level, where the call blinds at all (the G1 ones use the arena: before any
+// carving).
+int ensure_blinding_tables(bgn_ctx* c, int level, const uint8_t* r_be) {
+  if (!r_be) return BGN_OK;
+  return level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
+}
+
+// The end of every call that may blind: the result O (plain) takes Q^r / e(Q,Q)^r where r_be is set and goes to wire
+// bytes.  T1 / T2 / prefix are the scratch of blind_l1 / blind_l2 (unused without r_be, prefix on level 1 only).
+void blind_encode(bgn_ctx* c, hipStream_t s, int level, SoA2 O, const uint8_t* r_be, size_t r_len, SoA2 T1, SoA2 T2,
+                  uint32_t* prefix, size_t n, uint8_t* out) {
+  if (r_be && level == 1) blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, n);
+  else if (r_be) blind_l2(c, s, O, r_be, r_len, T1, T2, n);
+  c->kt->encode(s, level == 1 ? O.inf : nullptr, O.c0, O.c1, O.stride, c->L, n, out);
+}
+
+// The blinded tail of the aggregate calls.  Blinded, the call's last launch writes its wire bytes to a workspace array
+// (dst) instead of `out`, and finish() takes them through the path of the blinded Add — one fixed-base product per
+// element (bgn.go:488-495 / :466-474) — on their way to `out`.  Without r_be every member is a no-op.
+struct BlindTail {
+  int level;
+  const uint8_t* r_be;
+  size_t r_len;
+  size_t n = 0;
+  uint8_t* res = nullptr;
+  SoA2 O{}, T1{}, T2{};
+  uint32_t* prefix = nullptr;
+  // last in the call's layout: n elements of E wire bytes each
+  void take(Ws& w, size_t n_, size_t E) {
+    if (!r_be) return;
+    n = n_;
+    const size_t st = round_up(n, 64);
+    res = (uint8_t*)w.cv.take(n * E + 16);
+    O = w.elems(level, st); T1 = w.elems(level, st); T2 = w.elems(level, st);
+    if (level == 1) prefix = w.fp(st);
+  }
+  uint8_t* dst(uint8_t* out) const { return r_be ? res : out; }
+  void finish(bgn_ctx* c, hipStream_t s, uint8_t* out) const {
+    if (!r_be) return;
+    c->kt->decode_plain(s, c->d_params, res, c->L, n, O);
+    blind_encode(c, s, level, O, r_be, r_len, T1, T2, prefix, n, out);
+  }
+};
+
 int addsub_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint8_t* b, const uint8_t* r_be, size_t r_len,
                uint8_t* out, hipStream_t s, bool subtract) {
   if (!c || (count && (!a || !b || !out))) return fail(BGN_E_ARG, "null argument");
@@ -1611,10 +1655,7 @@ int addsub_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint
   std::lock_guard<std::mutex> lk(c->mu);
   StreamOrder order(c, s);
   HIP_TRY(hipSetDevice(c->device));
-  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
-    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
-    if (rc) return rc;
-  }
+  if (int rc = ensure_blinding_tables(c, level, r_be)) return rc;
   if (level == 1 && !r_be && c->kt->g1_add_wire && c->stream_codec && ((uintptr_t)out & 3u) == 0 && opt(c, &Options::l1_fused)) {
     // deterministic Add / Sub of level-1 ciphertexts: one wire-to-wire launch; the workspace is the prefix products
     // of the lanes' runs (one F_p per element)
@@ -1642,16 +1683,12 @@ int addsub_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint
     return BGN_OK;
   }
   const size_t st = round_up(count, 64);
-  SoA2 A, B, O, T1, T2;
+  SoA2 A, B, O, T1{}, T2{};
   uint32_t* prefix = nullptr;
   if (int rc = carve(c, [&](Ws& w) {
-    if (level == 1) {
-      A = w.g1(st); B = w.g1(st); O = w.g1(st); prefix = w.fp(st);
-      if (r_be) { T1 = w.g1(st); T2 = w.g1(st); }
-    } else {
-      A = w.gt(st); B = w.gt(st); O = w.gt(st);
-      if (r_be) { T1 = w.gt(st); T2 = w.gt(st); }
-    }
+    A = w.elems(level, st); B = w.elems(level, st); O = w.elems(level, st);
+    if (level == 1) prefix = w.fp(st);
+    if (r_be) { T1 = w.elems(level, st); T2 = w.elems(level, st); }
   })) return rc;
   const KernelTable* kt = c->kt;
   if (level == 1) {
@@ -1664,19 +1701,11 @@ int addsub_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, const uint
     kt->decode(s, c->d_params, b, c->L, count, B, nullptr, nullptr);
   }
   HIP_TRY(hipEventRecord(c->ev0, s));
-  if (level == 1) {
-    g1_add_launch(c, s, A, B, O, prefix, count, subtract, true);
-    HIP_TRY(hipEventRecord(c->ev1, s));
-    c->last_kernel = "k_g1_add";
-    if (r_be) blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, count);
-    kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, count, out);
-  } else {
-    gt_mul_launch(c, s, A, B, O, count, subtract, true);
-    HIP_TRY(hipEventRecord(c->ev1, s));
-    c->last_kernel = "k_gt_mul";
-    if (r_be) blind_l2(c, s, O, r_be, r_len, T1, T2, count);
-    kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, count, out);
-  }
+  if (level == 1) g1_add_launch(c, s, A, B, O, prefix, count, subtract, true);
+  else gt_mul_launch(c, s, A, B, O, count, subtract, true);
+  HIP_TRY(hipEventRecord(c->ev1, s));
+  c->last_kernel = level == 1 ? "k_g1_add" : "k_gt_mul";
+  blind_encode(c, s, level, O, r_be, r_len, T1, T2, prefix, count, out);
   c->ev_valid = true;
   HIP_TRY(hipGetLastError());
   return BGN_OK;
@@ -1713,6 +1742,47 @@ int sum_check(const bgn_ctx* c, size_t nseg, size_t seg_len, int level, const ui
   if (seg_len > kMaxBatch || nseg > kMaxBatch / seg_len) return fail(BGN_E_ARG, "batch too large (max 2^28 elements per call)");
   return BGN_OK;
 }
+
+// Level 2 at up to 40 limbs reduces wire bytes with the Barrett constants (sumops.hpp, barrett.hpp): a context that
+// holds none has no such kernel.
+bool wire_reduce_ok(const bgn_ctx* c, int level) { return !(level == 2 && c->nl <= 40 && !c->d_barrett); }
+
+// lanes a pass wants busy and the shortest run of a lane: the measured optimum per level at 2^20 elements of a 1024-bit
+// key (profiles/r10_sum_rates.csv) — level 1 pays a conversion per lane per pass, level 2 only the partials' traffic
+size_t level_lanes(int level) { return level == 1 ? kSumChipLanes : 2 * kSumChipLanes; }
+int64_t level_run_min(int level) { return level == 1 ? 4 : 2; }
+
+// The fold of wire arrays: the passes of `plan` over nout segments, the partials of a pass in two workspace arrays in
+// turns, the last pass into `last`.  An empty plan (a linear map of one chunk) takes nothing and launches nothing.
+struct WireFold {
+  size_t nout;
+  int level;
+  SumPlan plan;
+  size_t cap[2] = {0, 0};              // elements of the two arrays of partials
+  uint8_t* part[2] = {nullptr, nullptr};
+  // the plan of the level's defaults, or of what the caller's options ask for
+  static SumPlan planned(size_t nout, size_t seg_len, int level, int64_t want_lanes = 0, int64_t split = -1, int64_t want_run = 0) {
+    return plan_sum(nout, seg_len, want_lanes > 0 ? (size_t)want_lanes : level_lanes(level), split,
+                    want_run > 0 ? want_run : level_run_min(level));
+  }
+  WireFold(size_t nout_, int level_, const SumPlan& plan_) : nout(nout_), level(level_), plan(plan_) {
+    for (int k = 0; k + 1 < plan.passes; ++k)
+      if (nout * plan.split[k] > cap[k & 1]) cap[k & 1] = nout * plan.split[k];
+  }
+  void take(Ws& w, size_t E) {
+    for (int i = 0; i < 2; ++i)
+      if (cap[i]) part[i] = (uint8_t*)w.cv.take(cap[i] * E + 16);
+  }
+  // in: nout segments of len wire elements
+  void run(bgn_ctx* c, hipStream_t s, const uint8_t* in, uint32_t len, uint8_t* last) const {
+    for (int k = 0; k < plan.passes; ++k) {
+      uint8_t* dst = k + 1 < plan.passes ? part[k & 1] : last;
+      c->kt->sum_wire(s, c->d_params, c->d_consts, c->d_barrett, level, in, c->L, nout, len, plan.split[k], dst);
+      in = dst;
+      len = plan.split[k];
+    }
+  }
+};
 }  // namespace
 
 int bgn_sum_batch_dev(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const uint8_t* ct, const uint8_t* r_be,
@@ -1723,58 +1793,22 @@ int bgn_sum_batch_dev(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const 
   std::lock_guard<std::mutex> lk(c->mu);
   StreamOrder order(c, s);
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->kt->sum_wire || (level == 2 && c->nl <= 40 && !c->d_barrett))
-    return fail(BGN_E_PARAM, "no sum kernel for these parameters");
-  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
-    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
-    if (rc) return rc;
-  }
-  // lanes a pass wants busy and the shortest run of a lane: the measured optimum per level at 2^20 elements of a 1024-bit
-  // key (profiles/r10_sum_rates.csv) — level 1 pays a conversion per lane per pass, level 2 only the partials' traffic
-  const int64_t want_lanes = opt(c, &Options::sum_lanes), want_run = opt(c, &Options::sum_run_min);
-  const SumPlan plan = plan_sum(nseg, seg_len, want_lanes > 0 ? (size_t)want_lanes : (level == 1 ? kSumChipLanes : 2 * kSumChipLanes),
-                                opt(c, &Options::sum_split), want_run > 0 ? want_run : (level == 1 ? 4 : 2));
+  if (!c->kt->sum_wire || !wire_reduce_ok(c, level)) return fail(BGN_E_PARAM, "no sum kernel for these parameters");
+  if (int rc = ensure_blinding_tables(c, level, r_be)) return rc;
+  WireFold fold(nseg, level, WireFold::planned(nseg, seg_len, level, opt(c, &Options::sum_lanes), opt(c, &Options::sum_split),
+                                               opt(c, &Options::sum_run_min)));
+  BlindTail tail{level, r_be, r_len};  // once per segment
   const size_t E = 2 * (size_t)c->L;
-  size_t cap[2] = {0, 0};              // elements of the two arrays of partials
-  for (int k = 0; k + 1 < plan.passes; ++k)
-    if (nseg * plan.split[k] > cap[k & 1]) cap[k & 1] = nseg * plan.split[k];
-  const size_t st = round_up(nseg, 64);
-  uint8_t* part[2] = {nullptr, nullptr};
-  uint8_t* res = nullptr;
-  SoA2 O, T1, T2;
-  uint32_t* prefix = nullptr;
   if (int rc = carve(c, [&](Ws& w) {
-    for (int i = 0; i < 2; ++i)
-      if (cap[i]) part[i] = (uint8_t*)w.cv.take(cap[i] * E + 16);
-    if (r_be) {
-      res = (uint8_t*)w.cv.take(nseg * E + 16);
-      if (level == 1) { O = w.g1(st); T1 = w.g1(st); T2 = w.g1(st); prefix = w.fp(st); }
-      else { O = w.gt(st); T1 = w.gt(st); T2 = w.gt(st); }
-    }
+    fold.take(w, E);
+    tail.take(w, nseg, E);
   })) return rc;
-  const KernelTable* kt = c->kt;
   HIP_TRY(hipEventRecord(c->ev0, s));
-  const uint8_t* in = ct;
-  uint32_t len = (uint32_t)seg_len;
-  for (int k = 0; k < plan.passes; ++k) {
-    uint8_t* dst = k + 1 < plan.passes ? part[k & 1] : (r_be ? res : out);
-    kt->sum_wire(s, c->d_params, c->d_consts, c->d_barrett, level, in, c->L, nseg, len, plan.split[k], dst);
-    in = dst;
-    len = plan.split[k];
-  }
+  fold.run(c, s, ct, (uint32_t)seg_len, tail.dst(out));
   HIP_TRY(hipEventRecord(c->ev1, s));
   c->last_kernel = level == 1 ? "k_sum_g1_wire" : "k_sum_gt_wire";
   c->ev_valid = true;
-  if (r_be) {                          // bgn.go:488-495 / :466-474, once per segment
-    kt->decode_plain(s, c->d_params, res, c->L, nseg, O);
-    if (level == 1) {
-      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, nseg);
-      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, nseg, out);
-    } else {
-      blind_l2(c, s, O, r_be, r_len, T1, T2, nseg);
-      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, nseg, out);
-    }
-  }
+  tail.finish(c, s, out);
   HIP_TRY(hipGetLastError());
   return BGN_OK;
 }
@@ -1800,6 +1834,50 @@ int lincomb_check(const bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int lev
   return BGN_OK;
 }
 
+// What the planners of the maps may spend on tables.  A table entry: level 1 x, y, Z, prefix and a flag; level 2 re, im.
+// Half of what the context may still take goes to the tables, the rest to the other arrays of the call.
+struct TableBudget {
+  size_t entry_bytes, bytes;
+};
+TableBudget lin_table_budget(bgn_ctx* c, int level) {
+  size_t avail = 0;
+  if (!ctx_free_memory(c, &avail, c->arena_bytes)) avail = 0;
+  return {level == 1 ? 4 * (size_t)c->nl * 4 + 1 : 2 * (size_t)c->nl * 4, avail / 2};
+}
+
+// The window tables of the dense and the sparse map (linops.hpp k_lin_table): H = 2^(omega-1) entries per decoded
+// ciphertext, none at window width 1.
+struct LinTables {
+  int level;
+  size_t ncols, entries;
+  int H;
+  SoA2 T{};
+  uint32_t *tz = nullptr, *tp = nullptr;
+  void take(Ws& w) {
+    if (!entries) return;
+    const size_t st = round_up(entries, 64);
+    T = w.elems(level, st);
+    if (level == 1) { tz = w.fp(st); tp = w.fp(st); }
+  }
+  // after the caller's digit kernel: builds T from the decoded A and closes the timed auxiliary stage
+  int build(bgn_ctx* c, hipStream_t s, SoA2 A, const char* digits_kernel) {
+    if (entries) {
+      LinTableArgs ta;
+      ta.cx = A.c0; ta.cy = A.c1; ta.cinf = A.inf; ta.sc = A.stride;
+      ta.tx = T.c0; ta.ty = T.c1; ta.tinf = T.inf; ta.st = T.stride;
+      ta.tz = tz; ta.tp = tp;
+      ta.ncols = ncols; ta.H = H;
+      c->kt->lin_table(s, c->d_params, c->d_consts, level, ta);
+    } else {
+      T = A;                             // window width 1: the entries are the elements themselves
+    }
+    HIP_TRY(hipEventRecord(c->ev3, s));
+    c->ev2_valid = true;
+    c->aux_kernel = !entries ? digits_kernel : level == 1 ? "k_lin_table_g1" : "k_lin_table_gt";
+    return BGN_OK;
+  }
+};
+
 // The path without tables (bucketops.hpp), planned by dispatch.hpp plan_lincomb_buckets: the vectors are decoded once,
 // the columns sorted by the digits of their weights (count, offsets, scatter: nothing is read back), the buckets summed
 // by the reduce passes and folded; the tail — encode, blinding — is that of the table path.  Called with the context
@@ -1809,23 +1887,19 @@ int lincomb_buckets_dev(bgn_ctx* c, const BktPlan& bp, size_t nvec, size_t nrows
   const KernelTable* kt = c->kt;
   const size_t ncols = nvec * d, nout = nvec * nrows, E = 2 * (size_t)c->L, nb = bp.nb, R = bp.R;
   const size_t sc = round_up(ncols, 64), so = round_up(nout, 64);
-  SoA2 A, Pt[2], W, O, T1, T2;
-  uint32_t *ent = nullptr, *cnt = nullptr, *rs = nullptr, *cur = nullptr, *prefix = nullptr;
-  uint8_t* res = nullptr;
+  SoA2 A, Pt[2], W;
+  uint32_t *ent = nullptr, *cnt = nullptr, *rs = nullptr, *cur = nullptr;
+  BlindTail tail{level, r_be, r_len};  // once per output
   if (int rc = carve(c, [&](Ws& ws) {
-    A = level == 1 ? ws.g1(sc) : ws.gt(sc);
+    A = ws.elems(level, sc);
     ent = (uint32_t*)ws.cv.take(bp.nruns[0] * R * 4);
     cnt = (uint32_t*)ws.cv.take((size_t)(bp.npass + 1) * nb * 4);
     rs = (uint32_t*)ws.cv.take((size_t)bp.npass * nb * 4);
     cur = (uint32_t*)ws.cv.take(nb * 4);
     for (int i = 0; i < 2; ++i)
-      Pt[i] = level == 1 ? ws.g1(round_up(nvec * bp.cap[i], 64)) : ws.gt(round_up(nvec * bp.cap[i], 64));
-    W = level == 1 ? ws.g1(so) : ws.gt(so);
-    if (r_be) {
-      res = (uint8_t*)ws.cv.take(nout * E + 16);
-      if (level == 1) { O = ws.g1(so); T1 = ws.g1(so); T2 = ws.g1(so); prefix = ws.fp(so); }
-      else { O = ws.gt(so); T1 = ws.gt(so); T2 = ws.gt(so); }
-    }
+      Pt[i] = ws.elems(level, round_up(nvec * bp.cap[i], 64));
+    W = ws.elems(level, so);
+    tail.take(ws, nout, E);
   })) return rc;
   kt->decode(s, c->d_params, ct, c->L, ncols, A, nullptr, nullptr);
   HIP_TRY(hipEventRecord(c->ev2, s));
@@ -1870,20 +1944,11 @@ int lincomb_buckets_dev(bgn_ctx* c, const BktPlan& bp, size_t nvec, size_t nrows
     kt->bkt_fold(s, c->d_params, c->d_consts, level, fa);
     at ^= 1;
   }
-  kt->encode(s, level == 1 ? W.inf : nullptr, W.c0, W.c1, W.stride, c->L, nout, r_be ? res : out);
+  kt->encode(s, level == 1 ? W.inf : nullptr, W.c0, W.c1, W.stride, c->L, nout, tail.dst(out));
   HIP_TRY(hipEventRecord(c->ev1, s));
   c->last_kernel = level == 1 ? "k_bkt_reduce_g1" : "k_bkt_reduce_gt";
   c->ev_valid = true;
-  if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
-    kt->decode_plain(s, c->d_params, res, c->L, nout, O);
-    if (level == 1) {
-      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, nout);
-      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, nout, out);
-    } else {
-      blind_l2(c, s, O, r_be, r_len, T1, T2, nout);
-      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, nout, out);
-    }
-  }
+  tail.finish(c, s, out);
   HIP_TRY(hipGetLastError());
   return BGN_OK;
 }
@@ -1899,21 +1964,14 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
   StreamOrder order(c, s);
   HIP_TRY(hipSetDevice(c->device));
   const KernelTable* kt = c->kt;
-  if (!kt->lin_walk || !kt->sum_wire || (level == 2 && c->nl <= 40 && !c->d_barrett))
+  if (!kt->lin_walk || !kt->sum_wire || !wire_reduce_ok(c, level))
     return fail(BGN_E_PARAM, "no linear-map kernel for these parameters");
-  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
-    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
-    if (rc) return rc;
-  }
+  if (int rc = ensure_blinding_tables(c, level, r_be)) return rc;
   const size_t ncols = nvec * d, nout = nvec * nrows, E = 2 * (size_t)c->L;
-  // a table entry: level 1 x, y, Z, prefix and a flag; level 2 re, im.  Half of what the context may still take goes to
-  // the tables, the rest to the other arrays of the call.
-  const size_t entry_bytes = level == 1 ? 4 * (size_t)c->nl * 4 + 1 : 2 * (size_t)c->nl * 4;
-  size_t avail = 0;
-  if (!ctx_free_memory(c, &avail, c->arena_bytes)) avail = 0;
+  const TableBudget budget = lin_table_budget(c, level);
   BktPlan bp;                          // the path without tables, where it is planned or forced and its workspace fits
   if (kt->bkt_reduce)
-    bp = plan_lincomb_buckets(nvec, nrows, d, w_bits, avail / 2, entry_bytes, 2 * (size_t)c->nl * 4 + 1, level,
+    bp = plan_lincomb_buckets(nvec, nrows, d, w_bits, budget.bytes, budget.entry_bytes, 2 * (size_t)c->nl * 4 + 1, level,
                               kSumChipLanes, opt(c, &Options::lin_window), opt(c, &Options::lin_split),
                               opt(c, &Options::lin_buckets), opt(c, &Options::lin_bucket_window),
                               opt(c, &Options::lin_bucket_run));
@@ -1921,46 +1979,38 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
   // "window" per bit plane, M entries per group — and the decode, the fold of the chunks and the tail are shared
   GrpPlan gp;
   if (kt->grp_walk)
-    gp = plan_lincomb_groups(nvec, nrows, d, w_bits, avail / 2, entry_bytes, level, kSumChipLanes,
+    gp = plan_lincomb_groups(nvec, nrows, d, w_bits, budget.bytes, budget.entry_bytes, level, kSumChipLanes,
                              opt(c, &Options::lin_window), opt(c, &Options::lin_split), opt(c, &Options::lin_groups));
   const LinPath path = lin_path(bp, gp, opt(c, &Options::lin_buckets), opt(c, &Options::lin_groups));
   if (path == LinPath::Buckets) return lincomb_buckets_dev(c, bp, nvec, nrows, d, level, ct, w, w_bits, r_be, r_len, out, s);
   const bool grp = path == LinPath::Groups;
-  LinPlan plan = plan_lincomb(nvec, nrows, d, w_bits, avail / 2, entry_bytes, level, kSumChipLanes,
+  LinPlan plan = plan_lincomb(nvec, nrows, d, w_bits, budget.bytes, budget.entry_bytes, level, kSumChipLanes,
                               opt(c, &Options::lin_window), opt(c, &Options::lin_split));
   if (grp) { plan.nchunk = gp.nchunk; plan.entries = gp.entries; plan.nwin = w_bits; }
   const size_t nchunk = plan.nchunk, npart = nout * nchunk;
-  const int H = 1 << (plan.omega - 1);
   // level 1 of the groups: the prefix products of one level's additions, 3^(g-1) per lane of the table kernel's launch
   const size_t grp_sp = grp && level == 1 ? round_up(nvec * gp.ngroups, 256) * ((2 * gp.M + 1) / 3) : 0;
-  SumPlan fold;
-  if (nchunk > 1) fold = plan_sum(nout, nchunk, level == 1 ? kSumChipLanes : 2 * kSumChipLanes, -1, level == 1 ? 4 : 2);
-  size_t cap[2] = {0, 0};              // elements of the two arrays of the fold's partials
-  for (int k = 0; k + 1 < fold.passes; ++k)
-    if (nout * fold.split[k] > cap[k & 1]) cap[k & 1] = nout * fold.split[k];
-  const size_t sc = round_up(ncols, 64), st = round_up(plan.entries ? plan.entries : 1, 64), sp = round_up(npart, 64),
-               so = round_up(nout, 64);
-  SoA2 A, T, W, O, T1, T2;
-  uint32_t *tz = nullptr, *tp = nullptr, *prefix = nullptr;
-  uint8_t *planes = nullptr, *pw = nullptr, *res = nullptr, *part[2] = {nullptr, nullptr};
+  LinTables tab{level, ncols, grp ? 0 : plan.entries, 1 << (plan.omega - 1)};
+  WireFold fold(nout, level, nchunk > 1 ? WireFold::planned(nout, nchunk, level) : SumPlan());
+  BlindTail tail{level, r_be, r_len};  // once per output
+  const size_t sc = round_up(ncols, 64), sp = round_up(npart, 64);
+  SoA2 A, G{}, W;                      // G, gtp: the groups' tables (a plan of groups always has entries)
+  uint32_t* gtp = nullptr;
+  uint8_t *planes = nullptr, *pw = nullptr;
   if (int rc = carve(c, [&](Ws& ws) {
-    A = level == 1 ? ws.g1(sc) : ws.gt(sc);
+    A = ws.elems(level, sc);
     planes = (uint8_t*)ws.cv.take(grp ? (size_t)w_bits * gp.ngroups * nrows * 2
                                       : (size_t)plan.nwin * d * nrows * (size_t)lin_digit_bytes(plan.omega));
-    if (plan.entries) {
-      T = level == 1 ? ws.g1(st) : ws.gt(st);
-      if (grp_sp) tp = ws.fp(grp_sp);
-      else if (level == 1) { tz = ws.fp(st); tp = ws.fp(st); }
+    if (grp) {
+      G = ws.elems(level, round_up(plan.entries, 64));
+      if (level == 1) gtp = ws.fp(grp_sp);
+    } else {
+      tab.take(ws);
     }
-    W = level == 1 ? ws.g1(sp) : ws.gt(sp);
+    W = ws.elems(level, sp);
     if (nchunk > 1) pw = (uint8_t*)ws.cv.take(npart * E + 16);
-    for (int i = 0; i < 2; ++i)
-      if (cap[i]) part[i] = (uint8_t*)ws.cv.take(cap[i] * E + 16);
-    if (r_be) {
-      res = (uint8_t*)ws.cv.take(nout * E + 16);
-      if (level == 1) { O = ws.g1(so); T1 = ws.g1(so); T2 = ws.g1(so); prefix = ws.fp(so); }
-      else { O = ws.gt(so); T1 = ws.gt(so); T2 = ws.gt(so); }
-    }
+    fold.take(ws, E);
+    tail.take(ws, nout, E);
   })) return rc;
   kt->decode(s, c->d_params, ct, c->L, ncols, A, nullptr, nullptr);
   HIP_TRY(hipEventRecord(c->ev2, s));
@@ -1971,8 +2021,8 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
     kt->grp_codes(s, ca);
     GrpTableArgs ta;
     ta.cx = A.c0; ta.cy = A.c1; ta.cinf = A.inf; ta.sc = A.stride;
-    ta.tx = T.c0; ta.ty = T.c1; ta.tinf = T.inf; ta.st = T.stride;
-    ta.tp = tp; ta.sp = grp_sp;
+    ta.tx = G.c0; ta.ty = G.c1; ta.tinf = G.inf; ta.st = G.stride;
+    ta.tp = gtp; ta.sp = grp_sp;
     ta.nvec = nvec; ta.d = d; ta.ngroups = gp.ngroups; ta.g = gp.g; ta.M = (int)gp.M;
     kt->grp_table(s, c->d_params, c->d_consts, level, ta);
     HIP_TRY(hipEventRecord(c->ev3, s));
@@ -1980,7 +2030,7 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
     c->aux_kernel = level == 1 ? "k_grp_table_g1" : "k_grp_table_gt";
     HIP_TRY(hipEventRecord(c->ev0, s));
     GrpWalkArgs ga;
-    ga.tx = T.c0; ga.ty = T.c1; ga.tinf = T.inf; ga.st = T.stride; ga.M = (int)gp.M;
+    ga.tx = G.c0; ga.ty = G.c1; ga.tinf = G.inf; ga.st = G.stride; ga.M = (int)gp.M;
     ga.codes = (const int16_t*)planes; ga.w_bits = w_bits;
     ga.ox = W.c0; ga.oy = W.c1; ga.oinf = W.inf; ga.so = W.stride;
     ga.nvec = nvec; ga.nrows = nrows; ga.ngroups = gp.ngroups; ga.nchunk = nchunk;
@@ -1989,50 +2039,22 @@ int bgn_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d, int l
     LinDigitsArgs da;
     da.w = w; da.nrows = nrows; da.d = d; da.w_bits = w_bits; da.omega = plan.omega; da.planes = planes;
     kt->lin_digits(s, da);
-    if (plan.entries) {
-      LinTableArgs ta;
-      ta.cx = A.c0; ta.cy = A.c1; ta.cinf = A.inf; ta.sc = A.stride;
-      ta.tx = T.c0; ta.ty = T.c1; ta.tinf = T.inf; ta.st = T.stride;
-      ta.tz = tz; ta.tp = tp;
-      ta.ncols = ncols; ta.H = H;
-      kt->lin_table(s, c->d_params, c->d_consts, level, ta);
-    } else {
-      T = A;                             // window width 1: the entries are the elements themselves
-    }
-    HIP_TRY(hipEventRecord(c->ev3, s));
-    c->ev2_valid = true;
-    c->aux_kernel = !plan.entries ? "k_lin_digits" : level == 1 ? "k_lin_table_g1" : "k_lin_table_gt";
+    if (int rc = tab.build(c, s, A, "k_lin_digits")) return rc;
     HIP_TRY(hipEventRecord(c->ev0, s));
     LinWalkArgs wa;
-    wa.tx = T.c0; wa.ty = T.c1; wa.tinf = T.inf; wa.st = T.stride; wa.H = H;
+    wa.tx = tab.T.c0; wa.ty = tab.T.c1; wa.tinf = tab.T.inf; wa.st = tab.T.stride; wa.H = tab.H;
     wa.planes = planes; wa.omega = plan.omega; wa.nwin = plan.nwin;
     wa.ox = W.c0; wa.oy = W.c1; wa.oinf = W.inf; wa.so = W.stride;
     wa.nvec = nvec; wa.nrows = nrows; wa.d = d; wa.nchunk = nchunk;
     kt->lin_walk(s, c->d_params, c->d_consts, level, wa);
   }
-  uint8_t* last = r_be ? res : out;
+  uint8_t* last = tail.dst(out);
   kt->encode(s, level == 1 ? W.inf : nullptr, W.c0, W.c1, W.stride, c->L, npart, nchunk > 1 ? pw : last);
-  const uint8_t* in = pw;
-  uint32_t len = (uint32_t)nchunk;
-  for (int k = 0; k < fold.passes; ++k) {
-    uint8_t* dst = k + 1 < fold.passes ? part[k & 1] : last;
-    kt->sum_wire(s, c->d_params, c->d_consts, c->d_barrett, level, in, c->L, nout, len, fold.split[k], dst);
-    in = dst;
-    len = fold.split[k];
-  }
+  fold.run(c, s, pw, (uint32_t)nchunk, last);
   HIP_TRY(hipEventRecord(c->ev1, s));
   c->last_kernel = grp ? (level == 1 ? "k_grp_walk_g1" : "k_grp_walk_gt") : (level == 1 ? "k_lin_walk_g1" : "k_lin_walk_gt");
   c->ev_valid = true;
-  if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
-    kt->decode_plain(s, c->d_params, res, c->L, nout, O);
-    if (level == 1) {
-      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, nout);
-      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, nout, out);
-    } else {
-      blind_l2(c, s, O, r_be, r_len, T1, T2, nout);
-      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, nout, out);
-    }
-  }
+  tail.finish(c, s, out);
   HIP_TRY(hipGetLastError());
   return BGN_OK;
 }
@@ -2076,47 +2098,28 @@ int bgn_sparse_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d
   StreamOrder order(c, s);
   HIP_TRY(hipSetDevice(c->device));
   const KernelTable* kt = c->kt;
-  if (!kt->sp_walk || !kt->lin_table || !kt->sum_wire || (level == 2 && c->nl <= 40 && !c->d_barrett))
+  if (!kt->sp_walk || !kt->lin_table || !kt->sum_wire || !wire_reduce_ok(c, level))
     return fail(BGN_E_PARAM, "no sparse linear-map kernel for these parameters");
-  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
-    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
-    if (rc) return rc;
-  }
+  if (int rc = ensure_blinding_tables(c, level, r_be)) return rc;
   const size_t ncols = nvec * d, nout = nvec * nrows, E = 2 * (size_t)c->L;
-  const size_t entry_bytes = level == 1 ? 4 * (size_t)c->nl * 4 + 1 : 2 * (size_t)c->nl * 4;      // as for the dense map
-  size_t avail = 0;
-  if (!ctx_free_memory(c, &avail, c->arena_bytes)) avail = 0;
-  const size_t chip = level == 1 ? kSumChipLanes : 2 * kSumChipLanes;
-  const LinPlan plan = plan_sparse_lincomb(nvec, nrows, d, nnz, row_max, w_bits, avail / 2, entry_bytes, level, chip,
-                                           opt(c, &Options::lin_window), opt(c, &Options::lin_split));
+  const TableBudget budget = lin_table_budget(c, level);
+  const LinPlan plan = plan_sparse_lincomb(nvec, nrows, d, nnz, row_max, w_bits, budget.bytes, budget.entry_bytes, level,
+                                           level_lanes(level), opt(c, &Options::lin_window), opt(c, &Options::lin_split));
   const size_t nchunk = plan.nchunk, npart = nout * nchunk;
-  const int H = 1 << (plan.omega - 1);
-  SumPlan fold;
-  if (nchunk > 1) fold = plan_sum(nout, nchunk, chip, -1, level == 1 ? 4 : 2);
-  size_t cap[2] = {0, 0};              // elements of the two arrays of the fold's partials
-  for (int k = 0; k + 1 < fold.passes; ++k)
-    if (nout * fold.split[k] > cap[k & 1]) cap[k & 1] = nout * fold.split[k];
-  const size_t sc = round_up(ncols, 64), st = round_up(plan.entries ? plan.entries : 1, 64), sp = round_up(npart, 64),
-               so = round_up(nout, 64), nnz_pad = round_up(nnz ? nnz : 1, 64);
-  SoA2 A, T, W, O, T1, T2;
-  uint32_t *tz = nullptr, *tp = nullptr, *prefix = nullptr;
-  uint8_t *planes = nullptr, *pw = nullptr, *res = nullptr, *part[2] = {nullptr, nullptr};
+  LinTables tab{level, ncols, plan.entries, 1 << (plan.omega - 1)};
+  WireFold fold(nout, level, nchunk > 1 ? WireFold::planned(nout, nchunk, level) : SumPlan());
+  BlindTail tail{level, r_be, r_len};  // once per output
+  const size_t sc = round_up(ncols, 64), sp = round_up(npart, 64), nnz_pad = round_up(nnz ? nnz : 1, 64);
+  SoA2 A, W;
+  uint8_t *planes = nullptr, *pw = nullptr;
   if (int rc = carve(c, [&](Ws& ws) {
-    A = level == 1 ? ws.g1(sc) : ws.gt(sc);
+    A = ws.elems(level, sc);
     planes = (uint8_t*)ws.cv.take((size_t)plan.nwin * nnz_pad * (size_t)lin_digit_bytes(plan.omega));
-    if (plan.entries) {
-      T = level == 1 ? ws.g1(st) : ws.gt(st);
-      if (level == 1) { tz = ws.fp(st); tp = ws.fp(st); }
-    }
-    W = level == 1 ? ws.g1(sp) : ws.gt(sp);
+    tab.take(ws);
+    W = ws.elems(level, sp);
     if (nchunk > 1) pw = (uint8_t*)ws.cv.take(npart * E + 16);
-    for (int i = 0; i < 2; ++i)
-      if (cap[i]) part[i] = (uint8_t*)ws.cv.take(cap[i] * E + 16);
-    if (r_be) {
-      res = (uint8_t*)ws.cv.take(nout * E + 16);
-      if (level == 1) { O = ws.g1(so); T1 = ws.g1(so); T2 = ws.g1(so); prefix = ws.fp(so); }
-      else { O = ws.gt(so); T1 = ws.gt(so); T2 = ws.gt(so); }
-    }
+    fold.take(ws, E);
+    tail.take(ws, nout, E);
   })) return rc;
   kt->decode(s, c->d_params, ct, c->L, ncols, A, nullptr, nullptr);
   HIP_TRY(hipEventRecord(c->ev2, s));
@@ -2124,51 +2127,23 @@ int bgn_sparse_lincomb_batch_dev(bgn_ctx* c, size_t nvec, size_t nrows, size_t d
   da.w = w; da.col = col; da.nnz = nnz; da.nnz_pad = nnz_pad; da.d = d; da.w_bits = w_bits; da.omega = plan.omega;
   da.planes = planes;
   kt->sp_digits(s, da);
-  if (plan.entries) {
-    LinTableArgs ta;
-    ta.cx = A.c0; ta.cy = A.c1; ta.cinf = A.inf; ta.sc = A.stride;
-    ta.tx = T.c0; ta.ty = T.c1; ta.tinf = T.inf; ta.st = T.stride;
-    ta.tz = tz; ta.tp = tp;
-    ta.ncols = ncols; ta.H = H;
-    kt->lin_table(s, c->d_params, c->d_consts, level, ta);
-  } else {
-    T = A;                             // window width 1: the entries are the elements themselves
-  }
-  HIP_TRY(hipEventRecord(c->ev3, s));
-  c->ev2_valid = true;
-  c->aux_kernel = !plan.entries ? "k_sp_digits" : level == 1 ? "k_lin_table_g1" : "k_lin_table_gt";
+  if (int rc = tab.build(c, s, A, "k_sp_digits")) return rc;
   HIP_TRY(hipEventRecord(c->ev0, s));
   SpWalkArgs wa;
-  wa.tx = T.c0; wa.ty = T.c1; wa.tinf = T.inf; wa.st = T.stride; wa.H = H;
+  wa.tx = tab.T.c0; wa.ty = tab.T.c1; wa.tinf = tab.T.inf; wa.st = tab.T.stride; wa.H = tab.H;
   wa.planes = planes; wa.nnz_pad = nnz_pad; wa.omega = plan.omega; wa.nwin = plan.nwin;
   wa.row_ptr = row_ptr; wa.col = col;
   wa.ox = W.c0; wa.oy = W.c1; wa.oinf = W.inf; wa.so = W.stride;
   wa.nvec = nvec; wa.nrows = nrows; wa.d = d; wa.nnz = nnz; wa.nchunk = nchunk;
   wa.row_max = (uint32_t)(row_max < kMaxBatch ? row_max : kMaxBatch);       // (a row has at most nnz <= 2^28 entries)
   kt->sp_walk(s, c->d_params, c->d_consts, level, wa);
-  uint8_t* last = r_be ? res : out;
+  uint8_t* last = tail.dst(out);
   kt->encode(s, level == 1 ? W.inf : nullptr, W.c0, W.c1, W.stride, c->L, npart, nchunk > 1 ? pw : last);
-  const uint8_t* in = pw;
-  uint32_t len = (uint32_t)nchunk;
-  for (int k = 0; k < fold.passes; ++k) {
-    uint8_t* dst = k + 1 < fold.passes ? part[k & 1] : last;
-    kt->sum_wire(s, c->d_params, c->d_consts, c->d_barrett, level, in, c->L, nout, len, fold.split[k], dst);
-    in = dst;
-    len = fold.split[k];
-  }
+  fold.run(c, s, pw, (uint32_t)nchunk, last);
   HIP_TRY(hipEventRecord(c->ev1, s));
   c->last_kernel = level == 1 ? "k_sp_walk_g1" : "k_sp_walk_gt";
   c->ev_valid = true;
-  if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
-    kt->decode_plain(s, c->d_params, res, c->L, nout, O);
-    if (level == 1) {
-      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, nout);
-      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, nout, out);
-    } else {
-      blind_l2(c, s, O, r_be, r_len, T1, T2, nout);
-      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, nout, out);
-    }
-  }
+  tail.finish(c, s, out);
   HIP_TRY(hipGetLastError());
   return BGN_OK;
 }
@@ -2232,12 +2207,8 @@ int bgn_scan_batch_dev(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const
   std::lock_guard<std::mutex> lk(c->mu);
   StreamOrder order(c, s);
   HIP_TRY(hipSetDevice(c->device));
-  if (!c->kt->scan_wire || (level == 2 && c->nl <= 40 && !c->d_barrett))
-    return fail(BGN_E_PARAM, "no scan kernel for these parameters");
-  if (r_be) {                          // blinding base tables (G1 ones use the arena: before any carving)
-    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
-    if (rc) return rc;
-  }
+  if (!c->kt->scan_wire || !wire_reduce_ok(c, level)) return fail(BGN_E_PARAM, "no scan kernel for these parameters");
+  if (int rc = ensure_blinding_tables(c, level, r_be)) return rc;
   const size_t E = 2 * (size_t)c->L, count = nseg * seg_len;
   const size_t block = (size_t)fp_block(c->nl);
   // a quarter of what the context may still take goes to the sweeps' workspace: 16 * nl bytes per element of a launch,
@@ -2251,8 +2222,7 @@ int bgn_scan_batch_dev(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const
   }
   ScanRun run;
   run.c = c; run.s = s; run.level = level; run.nseg = nseg; run.jac = nullptr; run.lanes = 0;
-  run.plan = plan_scan(nseg, seg_len, level == 1 ? kSumChipLanes : 2 * kSumChipLanes, kScanRunMin, opt(c, &Options::scan_chunk),
-                       max_chunk);
+  run.plan = plan_scan(nseg, seg_len, level_lanes(level), kScanRunMin, opt(c, &Options::scan_chunk), max_chunk);
   const ScanPlan& plan = run.plan;
   size_t cmax = 0;
   if (level == 1) {                    // columns of the workspace: every lane of the widest level, or what the quarter holds
@@ -2265,38 +2235,21 @@ int bgn_scan_batch_dev(bgn_ctx* c, size_t nseg, size_t seg_len, int level, const
     const int64_t range = opt(c, &Options::scan_range);
     if (range >= 1 && run.lanes > round_up((size_t)range, block)) run.lanes = round_up((size_t)range, block);
   }
-  const size_t st = round_up(count, 64);
-  uint8_t* res = nullptr;
-  SoA2 O, T1, T2;
-  uint32_t* prefix = nullptr;
+  BlindTail tail{level, r_be, r_len};  // once per output
   if (int rc = carve(c, [&](Ws& w) {
     for (int k = 0; k + 1 < plan.levels; ++k) {
       run.tot[k] = (uint8_t*)w.cv.take(nseg * plan.nch[k] * E + 16);
       run.pre[k] = (uint8_t*)w.cv.take(nseg * plan.nch[k] * E + 16);
     }
     if (level == 1) run.jac = (uint32_t*)w.cv.take(cmax * per_elem * run.lanes);
-    if (r_be) {
-      res = (uint8_t*)w.cv.take(count * E + 16);
-      if (level == 1) { O = w.g1(st); T1 = w.g1(st); T2 = w.g1(st); prefix = w.fp(st); }
-      else { O = w.gt(st); T1 = w.gt(st); T2 = w.gt(st); }
-    }
+    tail.take(w, count, E);
   })) return rc;
   HIP_TRY(hipEventRecord(c->ev0, s));
-  scan_level(run, 0, ct, r_be ? res : out);
+  scan_level(run, 0, ct, tail.dst(out));
   HIP_TRY(hipEventRecord(c->ev1, s));
   c->last_kernel = level == 1 ? "k_scan_g1_wire" : "k_scan_gt_wire";
   c->ev_valid = true;
-  if (r_be) {                          // bgn.go:488-495 / :466-474, once per output
-    const KernelTable* kt = c->kt;
-    kt->decode_plain(s, c->d_params, res, c->L, count, O);
-    if (level == 1) {
-      blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, count);
-      kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, count, out);
-    } else {
-      blind_l2(c, s, O, r_be, r_len, T1, T2, count);
-      kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, count, out);
-    }
-  }
+  tail.finish(c, s, out);
   HIP_TRY(hipGetLastError());
   return BGN_OK;
 }
@@ -2323,7 +2276,7 @@ int bgn_neg_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* a, uin
   const size_t st = round_up(count, 64);
   SoA2 A;
   if (int rc = carve(c, [&](Ws& w) {
-    A = (level == 1) ? w.g1(st) : w.gt(st);
+    A = w.elems(level, st);
   })) return rc;
   const KernelTable* kt = c->kt;
   // Neg(c) = Sub(encryptZero(), c), bgn.go:436-438.  Level 1: (x, y) -> (x, p - y); level 2: 1 / c = conj(c) on
@@ -2391,10 +2344,7 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
   std::lock_guard<std::mutex> lk(c->mu);
   StreamOrder order(c, s);
   HIP_TRY(hipSetDevice(c->device));
-  if (r_be) {
-    int rc = level == 1 ? ensure_fixed_tables(c) : ensure_gt_table(c);
-    if (rc) return rc;
-  }
+  if (int rc = ensure_blinding_tables(c, level, r_be)) return rc;
   const size_t st = round_up(count, 64);
   // the lane groups take up to this many elements (a whole small batch, or the remainder of a large one)
   const size_t qlim = k_len <= 1024 ? multconst_quad_limit(dispatch_view(c), level, k_len) : 0;
@@ -2403,17 +2353,13 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
   const size_t qpiece = qlim > ((size_t)1 << 17) ? (size_t)1 << 17 : qlim;
   const size_t qmax = round_up(count < qpiece ? count : qpiece, 64);
   const size_t qws_bytes = !qlim ? 0 : 4 * (level == 1 ? quad_g1_mul_ws_words(c->nl, qmax, k_len) : quad_gt_pow_each_ws_words(c->nl, qmax));
-  SoA2 A, O, T1, T2;
+  SoA2 A, O, T1{}, T2{};
   uint32_t* prefix = nullptr;
   uint32_t* qws = nullptr;
   if (int rc = carve(c, [&](Ws& w) {
-    if (level == 1) {
-      A = w.g1(st); O = w.g1(st);
-      if (r_be) { T1 = w.g1(st); T2 = w.g1(st); prefix = w.fp(st); }
-    } else {
-      A = w.gt(st); O = w.gt(st);
-      if (r_be) { T1 = w.gt(st); T2 = w.gt(st); }
-    }
+    A = w.elems(level, st); O = w.elems(level, st);
+    if (r_be) { T1 = w.elems(level, st); T2 = w.elems(level, st); }
+    if (r_be && level == 1) prefix = w.fp(st);
     if (qws_bytes) qws = (uint32_t*)w.cv.take(qws_bytes);
   })) return rc;
   const KernelTable* kt = c->kt;
@@ -2469,13 +2415,7 @@ int bgn_multconst_batch_dev(bgn_ctx* c, size_t count, int level, const uint8_t* 
   }
   HIP_TRY(hipEventRecord(c->ev1, s));
   c->ev_valid = true;
-  if (level == 1) {
-    if (r_be) blind_l1(c, s, O, r_be, r_len, T1, T2, prefix, count);            // bgn.go:260-268
-    kt->encode(s, O.inf, O.c0, O.c1, O.stride, c->L, count, out);
-  } else {
-    if (r_be) blind_l2(c, s, O, r_be, r_len, T1, T2, count);                    // bgn.go:279-287
-    kt->encode(s, nullptr, O.c0, O.c1, O.stride, c->L, count, out);
-  }
+  blind_encode(c, s, level, O, r_be, r_len, T1, T2, prefix, count, out);        // bgn.go:260-268 / :279-287
   HIP_TRY(hipGetLastError());
   return BGN_OK;
 }

@@ -40,7 +40,7 @@ static size_t r256(size_t v) { return (v + 255) / 256 * 256; }
 static void run(int nl, size_t st, bool with_gt) {
   Ctx c;
   c.nl = nl;
-  SoA2 A{}, X{};
+  SoA2 A{}, X{}, E1{}, E2{};
   uint32_t* row = nullptr;
   uint8_t *one = nullptr, *odd = nullptr;
   int passes = 0;
@@ -51,6 +51,8 @@ static void run(int nl, size_t st, bool with_gt) {
     row = w.fp(st);
     one = (uint8_t*)w.cv.take(1);
     odd = (uint8_t*)w.cv.take(257);
+    E1 = w.elems(1, st);                                         // by level: a G1 array, then a GT array
+    E2 = w.elems(2, st);
   };
   CHECK(carve(&c, layout) == 0 && passes == 2);
   // by hand: limb arrays of nl * st u32, identity flags of st bytes
@@ -72,7 +74,13 @@ static void run(int nl, size_t st, bool with_gt) {
   add(row, (size_t)nl * st * 4, limb);
   add(one, 1, 256);
   add(odd, 257, 512);
+  add(E1.c0, (size_t)nl * st * 4, limb);
+  add(E1.c1, (size_t)nl * st * 4, limb);
+  add(E1.inf, st, r256(st));
+  add(E2.c0, (size_t)nl * st * 4, limb);
+  add(E2.c1, (size_t)nl * st * 4, limb);
   CHECK(A.stride == st && (!with_gt || (X.stride == st && X.inf == nullptr)));
+  CHECK(E1.stride == st && E2.stride == st && E2.inf == nullptr);
   CHECK(c.arena_bytes == off);                                   // 1. the sizing pass reports the carving pass's end
   for (size_t i = 0; i < want.size(); ++i) {
     const uint8_t* p = (const uint8_t*)want[i].p;
